@@ -2,7 +2,7 @@
 """Throughput of the gan-heightmaps train step on MI355X (BASELINE.json metric:
 "512px heightmap+texture train images/sec at 1/2/4/8 MI355X; % MFMA roofline").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -157,7 +157,39 @@ def parse_args(argv=None):
     ap.add_argument("--minimal", action="store_true",
                     help="timed region only: no steady-state loop, no host-array loops (counter-collection runs, where every "
                          "dispatch is serialised and a step takes seconds)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0, headline "
+                         "workload only): the five losses, and per network the parameters and gradients (a fixed seeded sample "
+                         "of DUMP_SAMPLE elements where larger) and the BatchNorm running statistics")
     return ap.parse_args(argv)
+
+
+DUMP_SAMPLE = 1 << 20           # elements kept per parameter / gradient array by --dump-outputs (4 MB each in float32)
+DUMP_LIMIT = 64 * 2 ** 20       # bytes written by --dump-outputs in all
+
+
+def dump_outputs(eng, losses, out_dir):
+    """--dump-outputs: the arrays the last timed step produced, for comparing two builds output for output.  The train step
+    returns the five losses (pix2pix.py:142 train_fn) and leaves its result in the parameter stores: the updated trainable
+    parameters, their gradients and the BatchNorm running statistics of every network.  A store larger than DUMP_SAMPLE
+    elements is sampled at indices drawn once from a fixed seed, so two runs with the same arguments dump the same elements."""
+    eng.sync()
+    arrays = {"losses": np.asarray(losses, np.float64)}
+    for k in sorted(eng.stores):
+        st = eng.stores[k]
+        n = st.n_train
+        idx = (np.sort(np.random.RandomState(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE
+               else np.arange(n))
+        arrays[k + ".params"] = st.w.numpy().ravel()[:n][idx]
+        arrays[k + ".grads"] = st.g.numpy().ravel()[:n][idx]
+        if st.n_state:
+            arrays[k + ".bn_state"] = st.s.numpy().ravel()[:st.n_state]
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def nominal_flops_per_step(b):
@@ -427,6 +459,10 @@ def measure(args, secondary_name=None):
     if comm is not None:
         elapsed = comm.max_scalar(elapsed)
     losses = eng._read_losses()
+    if args.dump_outputs and rank == 0 and not secondary_name:
+        # before anything below runs more steps on the same parameters
+        nbytes = dump_outputs(eng, losses, args.dump_outputs)
+        sys.stderr.write("bench.py: %.1f MB of outputs of the last timed step written to %s\n" % (nbytes / 2 ** 20, args.dump_outputs))
     if issue == 'recorded' and dominant:
         # replay r of plan p used slots base[p] + i + r * stride; the slots wrap modulo MAX_TIMERS: the last ``keep`` replays
         # of a plan still hold their events

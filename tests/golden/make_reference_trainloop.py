@@ -153,11 +153,12 @@ def main():
         lr = shared(np.float32(0.01))
         cb = KP.ReduceLROnPlateau(lr, **kw)
         cb.on_train_begin()
-        traj = []
+        traj, best = [], []
         for e, v in enumerate(plateau_sequence(len(kw))):
             cb.on_epoch_end(v, e + 1)
             traj.append([float(lr.get_value()), int(cb.wait), int(cb.cooldown_counter)])
-        out["plateau"].append({"kw": kw, "trajectory": traj})
+            best.append(float(cb.best))
+        out["plateau"].append({"kw": kw, "trajectory": traj, "best": best})
     out["provenance"] = "python tests/golden/make_reference_trainloop.py (reference pix2pix.py executed via lib2to3, not copied)"
     path = os.environ.get("GHM_FIXTURE_OUT") or os.path.join(HERE, "reference_trainloop.json")
     json.dump(out, open(path, "w"), indent=1)

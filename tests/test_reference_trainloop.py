@@ -82,25 +82,24 @@ def test_reduce_lr_on_plateau_matches_the_reference_fixture(case):
         assert [float(lr.get_value()), cb.wait, cb.cooldown_counter] == want, (case, e)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree only exists in the build container")
 @pytest.mark.parametrize("kw", [dict(), dict(mode='min', patience=2, factor=0.5), dict(mode='max', patience=1, cooldown=2),
                                 dict(mode='min', patience=0, factor=0.1, min_lr=1e-3, epsilon=0.01)])
-def test_reduce_lr_on_plateau_matches_the_reference_class(kw, monkeypatch):
-    """keras_ports.ReduceLROnPlateau (keras_ports.py:7-111), executed via lib2to3, against this package's class:
-    same learning-rate trajectory and internal counters on random monitor sequences"""
+def test_reduce_lr_on_plateau_matches_the_reference_class(kw):
+    """keras_ports.ReduceLROnPlateau (keras_ports.py:7-111), as the fixture generator recorded it executed via lib2to3
+    (reference_trainloop.json "plateau": learning rate, wait, cooldown counter and best value after every epoch),
+    against this package's class: same learning-rate trajectory and internal counters on random monitor sequences"""
     import numpy as np
     from gan_heightmaps_amd.keras_ports import ReduceLROnPlateau
     from gan_heightmaps_amd.updates import shared
-    monkeypatch.setattr(np, "Inf", np.inf, raising=False)      # the reference predates NumPy 2.0 (np.Inf removed)
-    M = _harness_module()
-    ref_mod = M.load_py2("/root/reference/keras_ports.py", "reference_keras_ports")
+    rec = next(r for r in FIX["plateau"] if r["kw"] == kw)
     rng = np.random.RandomState(len(kw))
     seq = np.round(1.5 + 0.2 * np.sin(np.arange(60) / 3.0) + 0.05 * rng.randn(60), 3).tolist()
-    lr_a, lr_b = shared(np.float32(0.01)), shared(np.float32(0.01))
-    a, b = ref_mod.ReduceLROnPlateau(lr_a, **kw), ReduceLROnPlateau(lr_b, **kw)
-    a.on_train_begin(); b.on_train_begin()
-    for e, v in enumerate(seq):
-        a.on_epoch_end(v, e + 1); b.on_epoch_end(v, e + 1)
-        assert float(lr_a.get_value()) == float(lr_b.get_value()), e
-        assert (a.wait, a.cooldown_counter, a.best) == (b.wait, b.cooldown_counter, b.best), e
+    assert len(rec["trajectory"]) == len(rec["best"]) == len(seq)
+    lr_b = shared(np.float32(0.01))
+    b = ReduceLROnPlateau(lr_b, **kw)
+    b.on_train_begin()
+    for e, (v, (lr_a, wait_a, cooldown_a), best_a) in enumerate(zip(seq, rec["trajectory"], rec["best"])):
+        b.on_epoch_end(v, e + 1)
+        assert lr_a == float(lr_b.get_value()), e
+        assert (wait_a, cooldown_a, best_a) == (b.wait, b.cooldown_counter, b.best), e
     assert float(lr_b.get_value()) < 0.01 or not kw
