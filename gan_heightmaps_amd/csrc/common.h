@@ -163,6 +163,8 @@ static inline void ghm_submit(ghm_ctx* ctx, F f) {
 }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+// launch shape of the flat wavefront kernels (elementwise.hip, optim.hip): ``total`` threads of 256, on the ctx stream
+#define EW_GRID(total) dim3(ceil_div((long)(total), 256)), dim3(256), 0, ctx->stream
 
 // activation and its derivative expressed through the OUTPUT (valid for all five kinds)
 // XCD-aware block remap: consecutive logical tiles (which share halo pixels / operand tiles) land on the same XCD's

@@ -1025,8 +1025,6 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 }
 __global__ void counter_tick_kernel(unsigned* counter) { *counter += 1u; }
 
-#define EW_GRID(total) dim3(ceil_div((long)(total), 256)), dim3(256), 0, ctx->stream
-
 // ---- small tensors: one block per channel does the whole layer (N * HW <= BN_SMALL_MAX values per channel) ----
 // The partial / final / apply form above is three dependent launches; for the 1x1 .. 64x64 maps of the U-Net bottleneck
 // and the first DCGAN stages those launches ARE the cost (chains of ~150 of them per step on the stage streams).

@@ -379,6 +379,10 @@ def conv_desc(N, Cc, H, W, K, kh, kw, stride, pad, x_nstride=None, y_nstride=Non
                     y_nstride if y_nstride is not None else K * Ho * Wo)
 
 
+# rule ids of ghm_opt_update (GHM_OPT_* in include/ghm.h)
+OPT_RULES = {'sgd': 0, 'momentum': 1, 'nesterov_momentum': 2, 'adagrad': 3, 'adadelta': 4, 'adamax': 5, 'amsgrad': 6}
+
+
 def _vp(x):
     if x is None:
         return C.c_void_p(0)
@@ -1011,6 +1015,14 @@ class Ops:
 
     def adam_tick(self, hyper):
         call("ghm_adam_tick", self.h, _vp(hyper))
+
+    def opt_update(self, rule, p, g, states, n, hyper, h=(), grad_scale=1.0):
+        """ghm_opt_update: ``rule`` a key of OPT_RULES, ``states`` its state buffers in the header's s0.. order, ``h`` its
+        constants h0.. (the table in include/ghm.h)"""
+        s = list(states) + [None] * (3 - len(states))
+        h = [float(v) for v in h] + [0.0] * (3 - len(h))
+        call("ghm_opt_update", self.h, OPT_RULES[rule], _vp(p), _vp(g), _vp(s[0]), _vp(s[1]), _vp(s[2]), int(n), _vp(hyper),
+             h[0], h[1], h[2], grad_scale)
 
     def grad_check(self, g, n):
         call("ghm_grad_check", self.h, _vp(g), int(n))

@@ -18,7 +18,7 @@ import numpy as np
 from . import init as _init
 from . import layers as L
 from .device import Device
-from .step import GanStep, TRAIN_KEYS
+from .step import GanStep, OPT_RULES, TRAIN_KEYS
 from .updates import adam, shared, OptimizerSpec
 from .util import convert_to_rgb, imsave, makedirs, plot_grid, writes as util_writes
 
@@ -62,8 +62,9 @@ class Pix2Pix:
         disc_fn_dcgan(in_shp, is_a_grayscale, **disc_params_dcgan) -> output layer
         gen_fn_p2p(in_shp, is_a_grayscale, is_b_grayscale, **gen_params_p2p) -> output layer
         disc_fn_p2p(in_shp, is_a_grayscale, is_b_grayscale, **disc_params_p2p) -> {"inputs": [a, b], "out": layer}
-        opt / opt_args: gan_heightmaps_amd.updates.{rmsprop, adam} and its kwargs; 'learning_rate' may be a
-        shared scalar (default adam with shared(1e-3), pix2pix.py:30)."""
+        opt / opt_args: a lasagne.updates rule of gan_heightmaps_amd.updates -- sgd, momentum, nesterov_momentum, adagrad,
+        rmsprop, adadelta, adam, adamax or amsgrad -- and its kwargs; 'learning_rate' may be a shared scalar, the
+        other hyper-parameters are numbers (default adam with shared(1e-3), pix2pix.py:30)."""
         assert train_mode in ['dcgan', 'p2p', 'both']
         assert reconstruction in ['l1', 'l2']
         if opt_args is None:
@@ -94,8 +95,8 @@ class Pix2Pix:
         self.dcgan = {'gen': dcgan_gen, 'disc': dcgan_disc}
         self.p2p = {'gen': p2p_gen, 'disc': p2p_disc["out"]}
         spec = opt(**opt_args)
-        if not isinstance(spec, OptimizerSpec):
-            raise TypeError("opt must be gan_heightmaps_amd.updates.rmsprop or .adam")
+        if not isinstance(spec, OptimizerSpec) or spec.kind not in OPT_RULES:
+            raise TypeError("opt must be one of gan_heightmaps_amd.updates.{%s}" % ", ".join(OPT_RULES))
         self.lr = opt_args['learning_rate'] if 'learning_rate' in opt_args else spec.learning_rate
         if device is None:
             # one process per GPU: the launcher's LOCAL_RANK names this process' device (a communicator brings its own)

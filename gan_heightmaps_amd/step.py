@@ -27,6 +27,42 @@ TRAIN_KEYS = ['dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_recon', 'p2p_disc']
 LANE_OF = {'dcgan_gen': 0, 'dcgan_disc': 0, 'p2p_gen': 1, 'p2p_disc': 1}
 
 
+class OptRule:
+    """one lasagne.updates rule as the engine runs it: the names of its per-parameter fp32 state buffers, whether it
+    advances the step counter hyper[1] (ghm_adam_tick, behind the update), and its launch
+    ``run(ops, p, g, states, n, hyper, hp, grad_scale)`` with ``states`` in ``slots`` order"""
+
+    def __init__(self, slots, ticks, run):
+        self.slots, self.ticks, self.run = slots, ticks, run
+
+
+def _opt_update(kind, consts):
+    return lambda o, p, g, s, n, hy, hp, gs: o.opt_update(kind, p, g, s, n, hy, [hp[c] for c in consts], gs)
+
+
+# keyed by OptimizerSpec.kind; update entries are labelled <kind>_<net> / <kind>_shard_<bucket>, ticks <kind>_tick_<net>
+OPT_RULES = {
+    'rmsprop': OptRule(('acc',), False,
+                       lambda o, p, g, s, n, hy, hp, gs: o.rmsprop(p, g, s[0], n, hy, hp['rho'], hp['epsilon'], gs)),
+    'adam': OptRule(('m', 'v'), True,
+                    lambda o, p, g, s, n, hy, hp, gs: o.adam(p, g, s[0], s[1], n, hy, hp['beta1'], hp['beta2'],
+                                                             hp['epsilon'], gs)),
+    'sgd': OptRule((), False, _opt_update('sgd', ())),
+    'momentum': OptRule(('velocity',), False, _opt_update('momentum', ('momentum',))),
+    'nesterov_momentum': OptRule(('velocity',), False, _opt_update('nesterov_momentum', ('momentum',))),
+    'adagrad': OptRule(('accu',), False, _opt_update('adagrad', ('epsilon',))),
+    'adadelta': OptRule(('accu', 'delta_accu'), False, _opt_update('adadelta', ('rho', 'epsilon'))),
+    'adamax': OptRule(('m', 'u'), True, _opt_update('adamax', ('beta1', 'beta2', 'epsilon'))),
+    'amsgrad': OptRule(('m', 'v', 'vhat'), True, _opt_update('amsgrad', ('beta1', 'beta2', 'epsilon'))),
+}
+
+
+def opt_rule(kind):
+    if kind not in OPT_RULES:
+        raise ValueError("unknown optimiser kind %r (known: %s)" % (kind, ", ".join(OPT_RULES)))
+    return OPT_RULES[kind]
+
+
 def _has_bn(layer):
     return any(isinstance(l, L.BatchNormLayer) for l in L.get_all_layers(layer))
 
@@ -140,18 +176,13 @@ class GanStep:
                        for k, v in self.nets.items()}
         # per-net optimiser state + hyper-parameter scalars [lr, t] in HBM
         self.hyper = {}
+        self.opt_rule = opt_rule(opt_spec.kind)
         lr = float(opt_spec.learning_rate.get_value()) if hasattr(opt_spec.learning_rate, 'get_value') \
             else float(opt_spec.learning_rate)
         for k, st in self.stores.items():
             d = self.devs[LANE_OF[k]]
             self.hyper[k] = d.tensor(np.array([lr, 0.0], np.float32))
-            n = st.n_pad
-            if opt_spec.kind == 'rmsprop':
-                st.opt_state = {'acc': d.zeros((1, n, 1, 1))}
-            elif opt_spec.kind == 'adam':
-                st.opt_state = {'m': d.zeros((1, n, 1, 1)), 'v': d.zeros((1, n, 1, 1))}
-            else:
-                raise ValueError(opt_spec.kind)
+            st.opt_state = {name: d.zeros((1, st.n_pad, 1, 1)) for name in self.opt_rule.slots}
         if hasattr(opt_spec.learning_rate, '_listeners'):
             opt_spec.learning_rate._listeners.append(self.set_lr)
         self.losses_dev = dev.zeros((1, 8, 1, 1))
@@ -507,7 +538,7 @@ class GanStep:
                 # (the communication stream has just waited for both stage streams: every kernel that reads the pre-update
                 # weights is behind it.)  Per sub-bucket, in the order it was reduced: this rank's shard of the optimiser
                 # update, then the all-gather of the updated parameter shards.
-                gs_, hp_ = 1.0 / self.world, self.opt_spec.hp
+                gs_, hp_, kind, rule = 1.0 / self.world, self.opt_spec.hp, self.opt_spec.kind, self.opt_rule
                 # forward order: the nets as the next step reads them (the generators of both stages first), a net's
                 # sub-buckets by ascending offset = first layers first; a per-net event behind its last gather
                 fwd_rank = {'dcgan_gen': 0, 'p2p_gen': 1, 'dcgan_disc': 2, 'p2p_disc': 3}
@@ -517,22 +548,17 @@ class GanStep:
                     st, hy, sh = self.stores[k], self.hyper[k], n // self.world
                     a0 = blo + self.rank * sh
                     wv, gv = st.w.channels(a0, a0 + sh), st.g.channels(a0, a0 + sh)
-                    if self.opt_spec.kind == 'rmsprop':
-                        av = st.opt_state['acc'].channels(a0, a0 + sh)
-                        b.exchange.append(("rmsprop_shard_" + label, lambda wv=wv, gv=gv, av=av, hy=hy, sh=sh: cops.rmsprop(
-                            wv, gv, av, sh, hy, hp_['rho'], hp_['epsilon'], gs_), None, cdev))
-                    else:
-                        mv, vv = st.opt_state['m'].channels(a0, a0 + sh), st.opt_state['v'].channels(a0, a0 + sh)
-                        b.exchange.append(("adam_shard_" + label, lambda wv=wv, gv=gv, mv=mv, vv=vv, hy=hy, sh=sh: cops.adam(
-                            wv, gv, mv, vv, sh, hy, hp_['beta1'], hp_['beta2'], hp_['epsilon'], gs_), None, cdev))
+                    sv = [st.opt_state[s].channels(a0, a0 + sh) for s in rule.slots]
+                    b.exchange.append((kind + "_shard_" + label, lambda wv=wv, gv=gv, sv=sv, hy=hy, sh=sh: rule.run(
+                        cops, wv, gv, sv, sh, hy, hp_, gs_), None, cdev))
                     full = st.w.channels(blo, blo + n)
                     b.exchange.append(("allgather_" + label[len("reducescatter_"):], lambda full=full, sh=sh: cops.all_gather(full, sh),
                                        None, cdev))
                     if last_of[k] == idx and k in gev:
                         b.exchange.append(("gathered_" + k, lambda ev=gev[k]: cdev.event_record(ev), None, cdev))
-                if self.opt_spec.kind == 'adam':
+                if rule.ticks:
                     for k in keys:
-                        b.exchange.append(("adam_tick_" + k, lambda hy=self.hyper[k]: cops.adam_tick(hy), None, cdev))
+                        b.exchange.append((kind + "_tick_" + k, lambda hy=self.hyper[k]: cops.adam_tick(hy), None, cdev))
 
             # one entry per stage stream, so that bench.py can bracket each with HIP events: the time a stage stream
             # spends in this wait is the EXPOSED part of the exchange
@@ -543,7 +569,7 @@ class GanStep:
                 if dB is not dA:
                     b.exchange.append(("wait_comm", lambda: dB.wait_for(cdev), None, dB))
         gs = 1.0 / self.world          # (x 1 / loss scale inside the optimiser kernels, from the device state)
-        hp = self.opt_spec.hp
+        hp, kind, rule = self.opt_spec.hp, self.opt_spec.kind, self.opt_rule
         b.update = [[], []]
         # one stream for both stages: one update list, so the fp16 sequence check* -> update* -> scale update is kept
         ulane = (lambda k: 0) if (self._ls_state and self.devs[1] is self.devs[0]) else (lambda k: LANE_OF[k])
@@ -557,14 +583,11 @@ class GanStep:
             st, hy = self.stores[k], self.hyper[k]
             lane = ulane(k)
             o = self.ops[lane]
-            if self.opt_spec.kind == 'rmsprop':
-                b.update[lane].append(("rmsprop_" + k, lambda st=st, hy=hy, o=o: o.rmsprop(
-                    st.w, st.g, st.opt_state['acc'], st.n_train, hy, hp['rho'], hp['epsilon'], gs)))
-            else:
-                b.update[lane].append(("adam_" + k, lambda st=st, hy=hy, o=o: o.adam(
-                    st.w, st.g, st.opt_state['m'], st.opt_state['v'], st.n_train, hy, hp['beta1'], hp['beta2'],
-                    hp['epsilon'], gs)))
-                b.update[lane].append(("adam_tick_" + k, lambda hy=hy, o=o: o.adam_tick(hy)))
+            sv = [st.opt_state[s] for s in rule.slots]
+            b.update[lane].append((kind + "_" + k, lambda st=st, sv=sv, hy=hy, o=o: rule.run(
+                o, st.w, st.g, sv, st.n_train, hy, hp, gs)))
+            if rule.ticks:
+                b.update[lane].append((kind + "_tick_" + k, lambda hy=hy, o=o: o.adam_tick(hy)))
         if self._ls_state:
             for lane in (0, 1):
                 if b.update[lane]:
