@@ -2,16 +2,20 @@
 """Throughput of the gan-heightmaps train step on MI355X (BASELINE.json metric:
 "512px heightmap+texture train images/sec at 1/2/4/8 MI355X; % MFMA roofline").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 A step = one call of the compiled train_fn of experiment test1_nobn_bilin_both (DCGAN G+D and pix2pix
 U-Net+PatchGAN forward, four gradient roots, four RMSprop updates) on a synthetic 512x512 batch of 4 per GPU
 (weak scaling) that is resident in HBM before the timed region.  Arithmetic: fp32 (the reference's floatX) by operand splitting on the bf16 matrix cores
 (dtype "bf16x3").  One process per GPU; gradients are summed
-with RCCL.  Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel, HIP events inside the
-timed region) and "cpu_baseline" (the numpy oracle on the host cores; rank 0, N=1 only).
+with RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  --full adds
+what takes runs of its own: "roofline" (dominant kernel, picked from instrumented steps and bracketed by HIP events inside
+the timed region), the thin-layer table, "exchange" (N > 1), the steady-state / lr = 0 / one-batch / host-array loops,
+"cpu_baseline" (the numpy oracle on the host cores; rank 0, N=1 only), the "secondary" configurations and the side file.
 """
 import argparse
 import json
@@ -115,11 +119,16 @@ def parse_args(argv=None):
     ap.add_argument("--issue", default="recorded", choices=["recorded", "eager"],
                     help="recorded (default): the step's multi-stream launch sequence is recorded once in libghm.so and "
                          "every step is ONE ghm_step_run call; eager: one C call per kernel from Python")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, thin-layer table and exchange figures, the steady-state / lr = 0 / "
+                         "one-batch / host-array loops, the CPU baseline, the secondary configurations and the side file "
+                         "(a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--one-stream", action="store_true", help="run both GAN stages on a single HIP stream")
     ap.add_argument("--no-grad-streams", action="store_true",
                     help="keep the weight/bias gradients on the stage's own stream (default: a second stream per stage)")
-    ap.add_argument("--profile", action="store_true", help="print a per-program-entry timing table to stderr")
+    ap.add_argument("--profile", action="store_true", help="print a per-program-entry timing table to stderr (the "
+                    "instrumented steps that --full takes the roofline from)")
     ap.add_argument("--ablate", default="", help="TUNING ONLY (results are wrong): comma-separated program-entry labels or "
                     "kernel-name prefixes whose launches are skipped, to see what a class of kernels costs inside the "
                     "overlapped schedule; the JSON line is marked invalid")
@@ -146,16 +155,16 @@ def parse_args(argv=None):
                          "update, all-gather of the updated parameters; allreduce_bf16 = the all-reduce through a bf16 exchange "
                          "buffer: half the bytes, REDUCED precision -- the JSON line says so in config.exchange)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="headline only: skip the short extra loops of BASELINE configs 1-5 (\"secondary\" key)")
+                    help="--full without the short extra loops of BASELINE configs 1-5 (\"secondary\" key)")
     ap.add_argument("--secondary-steps", type=int, default=12)
     ap.add_argument("--batches", type=int, default=8,
                     help="distinct synthetic batches resident in HBM that the timed steps rotate through (device-to-device "
                          "into the step's input buffers on a copy stream while the previous step runs); 1 = the same batch "
                          "every step (rounds 1-5; reported as value_single_batch)")
     ap.add_argument("--side-file", default=os.path.join("gpurun_out", "bench_secondary.json"),
-                    help="where the secondary configurations / thin-layer table / notes go (the stdout line stays < 4 KB)")
+                    help="--full: where the secondary configurations / thin-layer table / notes go (the stdout line stays < 4 KB)")
     ap.add_argument("--minimal", action="store_true",
-                    help="timed region only: no steady-state loop, no host-array loops (counter-collection runs, where every "
+                    help="--full without the steady-state and host-array loops (counter-collection runs, where every "
                          "dispatch is serialised and a step takes seconds)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0, headline "
@@ -332,9 +341,11 @@ def measure(args, secondary_name=None):
     dominant, launches_per_step, flops_per_step = None, 0, 0.0
     executed_flops_per_step = None
     thin_rows = []
-    if not args.graph:
-        # three instrumented (untimed) steps, per-entry median: every entry runs alone between two HIP events
-        runs = [eng.profile_train(B) for _ in range(3)]
+    # three instrumented (untimed) steps, per-entry median: every entry runs alone between two HIP events.  They train like
+    # any step, so a plain run takes them too and reads no time from them: its warm-up and timed steps then start from the
+    # parameters and the batch a --full run's start from
+    runs = None if args.graph else [eng.profile_train(B) for _ in range(3)]
+    if runs and (args.full or args.profile):
         table = [(r[0][0], sorted(x[1] for x in r)[1], r[0][2], r[0][3]) for r in zip(*runs)]
         by_kernel = {}
         for label, ms, meta, _lane in table:
@@ -430,6 +441,8 @@ def measure(args, secondary_name=None):
         eng.sync()
         inst_steps = args.steps
     else:
+        if issue == 'recorded' and runs:
+            run_steps(len(plans))               # the steps a --full run records its brackets in, unbracketed
         inst_steps = min(args.steps, 4000 // max(launches_per_step + 24 * (world > 1), 1)) if dominant else 0
 
     # ---- the W untimed warm-up steps, immediately in front of the timed region (the instrumented per-entry steps above leave
@@ -477,7 +490,7 @@ def measure(args, secondary_name=None):
     # wrap modulo MAX_TIMERS, so later replays would overwrite these event pairs
     timed_ms = [d.timer_ms(i) for d, i in timed]
     every_ms = {(id(d), i): d.timer_ms(i) for d, i, lab in every if lab is not None}
-    extras = (issue is not False and not args.ablate and not args.repeat and world == 1 and not secondary_name
+    extras = (args.full and issue is not False and not args.ablate and not args.repeat and world == 1 and not secondary_name
               and not args.minimal)
     # ---- steady state: the split kernels' rate is data- and clock-dependent (the bf16 matrix pipes are power-managed, DESIGN
     # section 4d): 60 more steps behind the timed region, reported beside ``value`` (never instead of it) ----
@@ -515,7 +528,7 @@ def measure(args, secondary_name=None):
     # ---- the same loop with the reference's host-array boundary (pix2pix.py:142: train_fn(Z, X, Y) takes numpy
     # arrays): every step uploads its 16 KB + 4 MB + 12 MB batch over PCIe before it is enqueued ----
     with_h2d = with_h2d_sync = None
-    if not args.ablate and world == 1 and not args.minimal:
+    if args.full and not args.ablate and world == 1 and not args.minimal:
         run = (lambda: eng.enqueue_train(b)) if issue is not False else (lambda: eng.enqueue_train(b, lambda lane, e: e[1]()))
         eng.sync()
         t1 = time.perf_counter()
@@ -606,7 +619,7 @@ def measure(args, secondary_name=None):
                                      "moved_* counts the q copy a first layer also writes",
                              "total_ms": round(sum(r["ms"] for r in thin_rows), 3), "launches": thin_rows} if thin_rows else None,
     }
-    if world > 1:
+    if world > 1 and args.full:
         # data-parallel exchange, measured inside the timed region: the all-reduce of every (sub-)bucket on the
         # communication stream, and -- the part of it that is EXPOSED -- how long each stage stream sat in its wait
         # for the communication stream before the optimiser updates
@@ -747,7 +760,7 @@ def main():
     out = measure(args)
     headline = (args.mode == "both" and args.dtype == "bf16x3" and not args.config1 and args.in_shp == 512
                 and args.batch_per_gpu == 4 and not args.graph and not args.one_stream and not args.no_grad_streams)
-    if rank == 0 and world == 1 and headline and not args.no_secondary and not args.ablate and not args.repeat:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_secondary and not args.ablate and not args.repeat:
         import copy
         sec = []
         for name, ov in SECONDARY:
@@ -773,9 +786,9 @@ def main():
                 "on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (dtype bf16x3; peak 2500 / 6 = 416.7 TFLOP/s fp32-equivalent); "
                 "passes the fp32 path's parity tests with the fp32 path's bounds in both modes (tests/test_gpu_split.py, "
                 "test_gpu_step.py, test_gpu_fullsize.py).  value_fp32_mfma: the same step on v_mfma_f32_32x32x2_f32 (--dtype f32)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.in_shp == 512 and not args.config1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.in_shp == 512 and not args.config1:
         out["cpu_baseline"] = cpu_baseline(2)
-    if rank == 0:
+    if rank == 0 and args.full:
         # the complete record (secondary configurations, thin-layer table, notes) goes to a side file ...
         try:
             side = args.side_file if os.path.isabs(args.side_file) else os.path.join(ROOT, args.side_file)
@@ -785,6 +798,7 @@ def main():
             out["side_file"] = args.side_file
         except OSError as ex:
             sys.stderr.write("bench.py: side file not written: %s\n" % ex)
+    if rank == 0:
         # ... and stdout carries ONE short JSON line
         print(headline_line(out), flush=True)
 

@@ -1,11 +1,18 @@
 """bench.py --dump-outputs: what the last timed step computed, written as float32 / float64 .npy files under a size cap,
-with the same sampled elements from run to run (checked on stand-in parameter stores: no GPU)."""
+with the same sampled elements from run to run (checked on stand-in parameter stores: no GPU); and on the GPU, the same
+outputs from a plain run as from a --full run."""
+import json
 import os
+import subprocess
+import sys
 import types
 
 import numpy as np
+import pytest
 
 import bench
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class _Buf:
@@ -62,3 +69,30 @@ def test_dump_outputs_option():
     assert bench.parse_args([]).dump_outputs is None
     a = bench.parse_args(["--steps", "7", "--dump-outputs", "out"])
     assert a.dump_outputs == "out" and a.steps == 7
+
+
+def test_full_option_is_off_by_default():
+    assert not bench.parse_args([]).full
+    assert bench.parse_args(["--full"]).full
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_a_full_run_dumps(tmp_path):
+    """a plain run leaves out what --full measures beside the headline, but takes the same training steps before its timed
+    region: the last timed step's outputs are bit-identical, and only the --full line carries the roofline"""
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-secondary", "--no-cpu-baseline", "--minimal",
+                                                   "--side-file", str(tmp_path / "side.json")])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["roofline"] is None and "cpu_baseline" not in plain and "side_file" not in plain
+    assert isinstance(full["roofline"], dict) and os.path.exists(tmp_path / "side.json")
+    assert plain["steps"] == full["steps"] == 3 and plain["warmup"] == full["warmup"] == 2 and plain["value"] > 0
+    assert plain["losses"] == full["losses"]
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == sorted(os.listdir(tmp_path / "full")) and "losses.npy" in files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f

@@ -6,22 +6,23 @@ R=${1:-r06}
 O=gpurun_out/refresh
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/${R}_bench.err          # the driver's command: headline + secondary lines
+ROOT=$(pwd)
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${R}_bench.json 2> $O/${R}_bench.err          # headline + secondary lines
 cp gpurun_out/bench_secondary.json $O/${R}_bench_secondary.json                                     # (its side file: the later runs overwrite it)
 for dt in f32 bf16 bf16x2 f16; do
-  python bench.py --steps 30 --warmup 5 --dtype $dt --no-cpu-baseline --no-secondary > $O/${R}_bench_$dt.json 2>> $O/${R}_bench.err
+  python bench.py --full --steps 30 --warmup 5 --dtype $dt --no-cpu-baseline --no-secondary > $O/${R}_bench_$dt.json 2>> $O/${R}_bench.err
 done
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-secondary > $O/${R}_bench_bf16x3_100steps.json 2>> $O/${R}_bench.err
-python bench.py --steps 10 --warmup 3 --in-shp 1024 --no-cpu-baseline --no-secondary > $O/${R}_bench_1024_bf16x3.json 2>> $O/${R}_bench.err
-python bench.py --steps 10 --warmup 3 --in-shp 1024 --dtype f16 --batch-per-gpu 2 --no-cpu-baseline --no-secondary > $O/${R}_bench_1024_f16_b2.json 2>> $O/${R}_bench.err
-python bench.py --steps 20 --warmup 3 --batch-per-gpu 8 --no-cpu-baseline --no-secondary > $O/${R}_bench_b8.json 2>> $O/${R}_bench.err
+python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-secondary > $O/${R}_bench_bf16x3_100steps.json 2>> $O/${R}_bench.err
+python bench.py --full --steps 10 --warmup 3 --in-shp 1024 --no-cpu-baseline --no-secondary > $O/${R}_bench_1024_bf16x3.json 2>> $O/${R}_bench.err
+python bench.py --full --steps 10 --warmup 3 --in-shp 1024 --dtype f16 --batch-per-gpu 2 --no-cpu-baseline --no-secondary > $O/${R}_bench_1024_f16_b2.json 2>> $O/${R}_bench.err
+python bench.py --full --steps 20 --warmup 3 --batch-per-gpu 8 --no-cpu-baseline --no-secondary > $O/${R}_bench_b8.json 2>> $O/${R}_bench.err
 for dt in bf16x3 bf16x2 f32; do
   GHM_PROFILE_ALL=1 python bench.py --steps 5 --profile --no-cpu-baseline --no-secondary --dtype $dt > /dev/null 2> $O/${R}_kernel_table_$dt.txt
 done
 bash tools/split_quick.sh > $O/${R}_split_kernels_alone.txt 2>&1
 for dt in bf16x3 bf16x2 f32; do
   rm -rf /tmp/prof_$dt
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$dt -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype $dt > $GRAFT_REPO_ROOT/$O/${R}_bench_under_rocprof_$dt.json 2>/dev/null)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$dt -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype $dt > $ROOT/$O/${R}_bench_under_rocprof_$dt.json 2>/dev/null)
   f=$(find /tmp/prof_$dt -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${R}_rocprofv3_kernel_stats_$dt.csv
 done
