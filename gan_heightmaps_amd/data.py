@@ -70,6 +70,15 @@ class Hdf5Iterator:
     def __iter__(self):
         return self
 
+    def get_state(self):
+        """the iterator's position: its shuffle / augmentation RNG and the slices left of the current pass"""
+        return {'rnd_state': self.rnd_state.get_state(), 'pending': [(s.start, s.stop) for s in self._pending]}
+
+    def set_state(self, state):
+        """continue from a get_state(): plan_next() then returns what the saved iterator would have returned"""
+        self.rnd_state.set_state(state['rnd_state'])
+        self._pending = [slice(a, b) for a, b in state['pending']]
+
     # ---- host-side plan of one batch (pure; tested against oracle/keras_aug.py on CPU) ----
     def _refill(self):
         if not self._pending:

@@ -33,6 +33,13 @@ class ArrayIterator:
     def __iter__(self):
         return self
 
+    def get_state(self):
+        return {'rng': self.rng.get_state(), 'slices': [(s.start, s.stop) for s in self._slices]}
+
+    def set_state(self, state):
+        self.rng.set_state(state['rng'])
+        self._slices = [slice(a, b) for a, b in state['slices']]
+
     def __next__(self):
         if not self._slices:
             self._slices = [slice(b * self.bs, (b + 1) * self.bs) for b in range((self.N + self.bs - 1) // self.bs)]

@@ -63,6 +63,19 @@ def opt_rule(kind):
     return OPT_RULES[kind]
 
 
+def crc_range(comm, crc):
+    """(min, max) over the ranks of a 32-bit CRC (every rank calls it; ``comm`` None: this process alone)"""
+    if comm is None:
+        return crc, crc
+    lo16, hi16 = float(crc & 0xffff), float(crc >> 16)          # exactly representable in fp32
+    mx = (comm.max_scalar(hi16), comm.max_scalar(lo16))
+    mn = (-comm.max_scalar(-hi16), -comm.max_scalar(-lo16))
+    return (int(mn[0]) << 16 | int(mn[1])), (int(mx[0]) << 16 | int(mx[1]))
+
+
+STATE_NETS = ('dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_disc')
+
+
 def _has_bn(layer):
     return any(isinstance(l, L.BatchNormLayer) for l in L.get_all_layers(layer))
 
@@ -259,12 +272,7 @@ class GanStep:
             st = self.stores[k]
             for t in (st.w, st.s):
                 crc = zlib.crc32(t.numpy().tobytes(), crc)
-        if self.comm is None or self.world == 1:
-            return crc, crc
-        lo16, hi16 = float(crc & 0xffff), float(crc >> 16)          # exactly representable in fp32
-        mx = (self.comm.max_scalar(hi16), self.comm.max_scalar(lo16))
-        mn = (-self.comm.max_scalar(-hi16), -self.comm.max_scalar(-lo16))
-        return (int(mn[0]) << 16 | int(mn[1])), (int(mx[0]) << 16 | int(mx[1]))
+        return crc_range(self.comm if self.world > 1 else None, crc)
 
     def set_lr(self, lr):
         self.sync()
@@ -272,6 +280,101 @@ class GanStep:
             cur = h.numpy().ravel()
             cur[0] = lr
             h.set(cur)
+
+    # ---- training state (checkpoint / resume) ------------------------------------------------------------
+    # Everything a step reads besides the parameters and the batch: per net the optimiser slots and hyper = [lr, t], the
+    # dropout step counters and the fp16 loss-scale records.  Restored IN PLACE: recorded programs and captured graphs hold
+    # these buffers' pointers.
+    def _counters(self):
+        """{(name, batch size): DevTensor} of every dropout counter that exists: the train plans' per (net, B) ('G' / 'U'),
+        the non-deterministic forward-only plans' per (net key, B)"""
+        out = {k: t for k, t in getattr(self, '_rng_counters', {}).items() if t is not None}
+        for (key, B, det), (plan, _) in self._infer.items():
+            if not det and plan.rng_counter is not None:
+                out[(key, B)] = plan.rng_counter
+        return out
+
+    def _apply_pending_counters(self):
+        """counters restored before their plan existed take their value when it is built"""
+        pend = getattr(self, '_pending_counters', None)
+        if not pend:
+            return
+        for key, t in self._counters().items():
+            if key in pend:
+                t.set(np.asarray([pend.pop(key)], np.uint32).view(np.float32))
+
+    def _state_header(self):
+        return {'kind': self.opt_spec.kind, 'hp': {k: float(v) for k, v in self.opt_spec.hp.items()},
+                'dtype': self.dtype, 'train_mode': self.train_mode}
+
+    def training_state(self):
+        """the engine's training state as host arrays (see restore_training_state).  Drains the input pipeline and every
+        stream first.  Sharded update (rs_ag): a rank's optimiser slots are current on its own shards only -- they are
+        all-gathered bucket by bucket first (a collective: every rank calls this), so the state is that of the whole net,
+        whatever the world size.  Otherwise the state is replicated and this rank's copy is it."""
+        self.close_pipeline()
+        self.sync()
+        if self.sharded and self.opt_rule.slots:
+            plans = [b for b in self._built.values() if getattr(b, 'xchg_order', None)]
+            if plans:       # (no step yet: the state is still the zeros every rank started from)
+                # the buckets are the same in every plan (they depend on the stores and the bucket size only)
+                for label, k, blo, n in plans[0].xchg_order:
+                    for s in self.opt_rule.slots:
+                        self.cops.all_gather(self.stores[k].opt_state[s].channels(blo, blo + n), n // self.world)
+                self.sync()
+        state = self._state_header()
+        state['nets'] = {}
+        for k in STATE_NETS:
+            st = self.stores[k]
+            state['nets'][k] = {
+                'n_train': st.n_train, 'n_state': st.n_state,
+                'hyper': self.hyper[k].numpy().ravel()[:2].copy(),
+                'slots': {s: st.opt_state[s].numpy().ravel()[:st.n_train].copy() for s in self.opt_rule.slots}}
+        counters = {k: int(t.numpy().ravel()[:1].view(np.uint32)[0]) for k, t in self._counters().items()}
+        counters.update(getattr(self, '_pending_counters', None) or {})       # restored, plan not built since
+        state['rng_counters'] = counters
+        state['loss_scale'] = self.loss_scale_state()
+        return state
+
+    def check_training_state(self, state):
+        """ValueError naming the first field in which ``state`` does not fit this engine"""
+        live = self._state_header()
+        for f in ('kind', 'hp', 'dtype', 'train_mode'):
+            if state.get(f) != live[f]:
+                raise ValueError("training state: %s is %r in the checkpoint, %r in this run" % (f, state.get(f), live[f]))
+        for k in STATE_NETS:
+            st, sv = self.stores[k], state['nets'].get(k, {})
+            for f in ('n_train', 'n_state'):
+                if sv.get(f) != getattr(st, f):
+                    raise ValueError("training state: %s of %s is %r in the checkpoint, %r in this run"
+                                     % (f, k, sv.get(f), getattr(st, f)))
+            if sorted(sv['slots']) != sorted(self.opt_rule.slots) or \
+                    any(np.asarray(v).size != st.n_train for v in sv['slots'].values()):
+                raise ValueError("training state: optimiser slots of %s do not fit %s" % (k, self.opt_spec.kind))
+        if len(state.get('loss_scale', [])) != len(self._ls_state):
+            raise ValueError("training state: %d loss-scale records in the checkpoint, %d in this run"
+                             % (len(state.get('loss_scale', [])), len(self._ls_state)))
+
+    def restore_training_state(self, state):
+        """inverse of training_state, into the existing buffers.  Every rank loads whole buffers (in the sharded form each
+        then updates its own shards, as before); padding is zeroed; dropout counters of plans not built yet are applied
+        when they are built, counters the checkpoint does not know restart at zero."""
+        self.check_training_state(state)
+        self.close_pipeline()
+        self.sync()
+        for k in STATE_NETS:
+            st, sv = self.stores[k], state['nets'][k]
+            for s in self.opt_rule.slots:
+                full = np.zeros(st.n_pad, np.float32)
+                full[:st.n_train] = np.asarray(sv['slots'][s], np.float32)
+                st.opt_state[s].set(full)
+            self.hyper[k].set(np.asarray(sv['hyper'], np.float32))
+        self._pending_counters = dict(state['rng_counters'])
+        for key, t in self._counters().items():
+            t.set(np.asarray([self._pending_counters.pop(key, 0)], np.uint32).view(np.float32))
+        if self._ls_state:
+            self.restore_loss_scale_state(state['loss_scale'])
+        self.sync()
 
     # ---- building -------------------------------------------------------------------------------------
     def _build(self, B, slot=0):
@@ -310,6 +413,7 @@ class GanStep:
                       rng_counter=rc.get(('U', B)))
         rc.setdefault(('G', B), b.G.rng_counter)
         rc.setdefault(('U', B), b.U.rng_counter)
+        self._apply_pending_counters()
         b.z = b.G.input_nodes[0].out
         b.x = b.U.input_tensor(u_in_layer)
         b.y = dB.empty((B,) + tuple(pb.shape[1:]))
@@ -998,6 +1102,7 @@ class GanStep:
             prog = []
             plan.emit_forward(prog, deterministic=deterministic)
             self._infer[k] = (plan, prog)
+            self._apply_pending_counters()
         return self._infer[k]
 
     def generate(self, key, inp, deterministic=False):
