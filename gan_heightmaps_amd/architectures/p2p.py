@@ -109,6 +109,23 @@ def discriminator2(in_shp, is_a_grayscale, is_b_grayscale, nf=32, act=sigmoid, m
                                 lambda idx: idx != 0)
 
 
+def pixel_discriminator(in_shp, is_a_grayscale, is_b_grayscale, nf=64, act=sigmoid, mul_factor=[1, 2], bn=False):
+    """1x1 "PixelGAN" discriminator: the PatchGAN's layer order with 1x1 stride-1 convolutions, so every output pixel
+    judges one input pixel (the experiment the reference's README proposes for patchy textures).  Returns
+    {"inputs": [layer_a, layer_b], "out": layer} with out (None, 1, in_shp, in_shp); the weights keep the lasagne
+    (K, C, 1, 1) layout.  The engine lowers it layer by layer like any other chain of convolutions."""
+    i_a = InputLayer((None, 1 if is_a_grayscale else 3, in_shp, in_shp))
+    i_b = InputLayer((None, 1 if is_b_grayscale else 3, in_shp, in_shp))
+    x = concatenate_layers([i_a, i_b])
+    for m in mul_factor:
+        x = Convolution(x, nf * m, k=1, s=1)
+        x = NonlinearityLayer(x, leaky_rectify)
+        if bn:
+            x = BatchNormLayer(x)              # after the nonlinearity, as in _patch_discriminator
+    x = Convolution(x, 1, k=1, s=1)
+    return {"inputs": [i_a, i_b], "out": NonlinearityLayer(x, act)}
+
+
 # debugging architectures (p2p.py:314-325)
 
 def fake_generator(is_a_grayscale, is_b_grayscale, act=tanh, in_shp=512):

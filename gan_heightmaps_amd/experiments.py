@@ -106,7 +106,7 @@ def get_iterators(dataset, batch_size, is_a_grayscale, is_b_grayscale, da=True, 
     return it_train, it_val
 
 
-# kwargs of the three experiments (experiments.py:24-41, :63-79, :102-119)
+# kwargs of the experiments (experiments.py:24-41, :63-79, :102-119)
 _COMMON = dict(
     gen_fn_dcgan=dcgan.default_generator, disc_fn_dcgan=dcgan.default_discriminator,
     gen_params_dcgan={'num_repeats': 0, 'div': [2, 2, 4, 4, 8, 8, 8]},
@@ -129,6 +129,12 @@ def experiment_kwargs(name):
     elif name == 'test1_nobn_bilin_both':
         kw['gen_params_p2p'] = {'nf': 64, 'act': tanh, 'num_repeats': 0, 'bilinear_upsample': True}
         kw['train_mode'] = 'both'
+    elif name == 'test1_nobn_bilin_both_pixeld':
+        # test1_nobn_bilin_both with the 1x1 pixel discriminator (not in the reference: the follow-up its README proposes)
+        kw['gen_params_p2p'] = {'nf': 64, 'act': tanh, 'num_repeats': 0, 'bilinear_upsample': True}
+        kw['train_mode'] = 'both'
+        kw['disc_fn_p2p'] = p2p.pixel_discriminator
+        kw['disc_params_p2p'] = {'nf': 64, 'bn': False, 'act': linear, 'mul_factor': [1, 2]}
     else:
         raise KeyError(name)
     return kw
@@ -199,9 +205,18 @@ def test1_nobn_bilin_both(mode, num_epochs=1000, **kw):
     return model
 
 
+def test1_nobn_bilin_both_pixeld(mode, num_epochs=1000, **kw):
+    """test1_nobn_bilin_both with the 1x1 pixel discriminator (architectures/p2p.py pixel_discriminator)"""
+    assert mode in ["train", "interp", "gen"]
+    model = make_model('test1_nobn_bilin_both_pixeld', **kw.pop('backend', {}))
+    if mode == "train":
+        _train(model, "test1_nobn_bilin_both_pixeld", num_epochs, **kw)
+    return model
+
+
 def main(argv):
     fn = {'test1_nobn': test1_nobn, 'test1_nobn_finetunep2p_bilin': test1_nobn_finetunep2p_bilin,
-          'test1_nobn_bilin_both': test1_nobn_bilin_both}[argv[1]]
+          'test1_nobn_bilin_both': test1_nobn_bilin_both, 'test1_nobn_bilin_both_pixeld': test1_nobn_bilin_both_pixeld}[argv[1]]
     fn(argv[2])
 
 
