@@ -43,6 +43,7 @@ SIGNATURES = {
     "ghm_host_alloc": [C.c_size_t, C.POINTER(_p)],
     "ghm_host_free": [_p],
     "ghm_h2d_async": [_p, _p, _p, C.c_size_t],
+    "ghm_d2h_async": [_p, _p, _p, C.c_size_t],
     "ghm_d2d": [_p, _p, _p, C.c_size_t],
     "ghm_memset_zero": [_p, _p, C.c_size_t],
     "ghm_sync": [_p],
@@ -157,6 +158,9 @@ SIGNATURES = {
     "ghm_scale_samples": [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _i64],
     "ghm_axpby": [_p, _f, _p, _f, _p, _i64],
     "ghm_image_batch": [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p, _i64],
+    "ghm_texture_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
+    "ghm_texture_blend": [_p, _p, _i32, _i32, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "ghm_texture_finalize": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_lsgan_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_bce_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_recon_loss": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _f, _i32],

@@ -227,6 +227,14 @@ int ghm_h2d_async(ghm_ctx* ctx, void* dst, const void* src_pinned, size_t bytes)
     return 0;
 }
 
+int ghm_d2h_async(ghm_ctx* ctx, void* dst_pinned, const void* src, size_t bytes) {
+    // the mirror of ghm_h2d_async: dst_pinned comes from ghm_host_alloc and is read only after the context's stream has
+    // passed this copy (an event recorded behind it, or ghm_sync)
+    GHM_CHECK(!ctx->capturing && !ctx->rec, "ghm_d2h_async inside a capture / recording");
+    GHM_HIP(hipMemcpyAsync(dst_pinned, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
 // persistent events: a point of one context's stream that other contexts wait for LATER (ghm_stream_wait can only name
 // "everything enqueued so far").  The input pipeline needs exactly that: the stage streams of step i wait for the upload of
 // ITS batch, not for whatever the copy stream was told to do after it.

@@ -252,9 +252,17 @@ class Device:
     def event_destroy(ev):
         call("ghm_event_destroy", ev)
 
-    def h2d_async(self, ptr, pinned):
-        """copy a PinnedArray to the device, ordered on this context's stream, without waiting for it"""
-        call("ghm_h2d_async", self.h, C.c_void_p(ptr), C.c_void_p(pinned.ptr), pinned.array.nbytes)
+    def h2d_async(self, ptr, pinned, nbytes=None):
+        """copy a PinnedArray (its first ``nbytes``) to the device, ordered on this context's stream, without waiting for it"""
+        n = pinned.array.nbytes if nbytes is None else int(nbytes)
+        assert n <= pinned.array.nbytes
+        call("ghm_h2d_async", self.h, C.c_void_p(ptr), C.c_void_p(pinned.ptr), n)
+
+    def d2h_async(self, pinned, ptr, nbytes):
+        """copy ``nbytes`` from the device into a PinnedArray, ordered on this context's stream, without waiting for it
+        (read the array only after an event recorded behind the copy has passed)"""
+        assert int(nbytes) <= pinned.array.nbytes
+        call("ghm_d2h_async", self.h, C.c_void_p(pinned.ptr), C.c_void_p(ptr), int(nbytes))
 
     def d2h(self, arr, ptr, nbytes):
         assert arr.flags['C_CONTIGUOUS']
@@ -992,6 +1000,20 @@ class Ops:
     def image_batch(self, src_u8_ptr, N, H, W, Cc, xform_ptr, tanh_range, dst):
         call("ghm_image_batch", self.h, C.c_void_p(int(src_u8_ptr)), N, H, W, Cc, C.c_void_p(int(xform_ptr)),
              int(tanh_range), _vp(dst), dst.nstride)
+
+    # tiled inference (csrc/texture.hip, gan_heightmaps_amd/texture.py)
+    def texture_gather(self, band_ptr, band_u8, Cc, band_rows, band_row0, H, W, y0, x0, stride, n_valid, tanh_range, dst):
+        call("ghm_texture_gather", self.h, C.c_void_p(int(band_ptr)), int(band_u8), Cc, band_rows, band_row0, H, W, y0, x0,
+             stride, n_valid, dst.N, dst.H, int(tanh_range), _vp(dst), dst.nstride)
+
+    def texture_blend(self, acc_ptr, W, T, Cc, u, nb, iy, ny, j0, nx, pad_x, overlap):
+        assert u.H == T and u.W == T and u.Cc == Cc and nb <= u.N
+        call("ghm_texture_blend", self.h, C.c_void_p(int(acc_ptr)), W, T, Cc, _vp(u), u.nstride, nb, iy, ny, j0, nx, pad_x,
+             overlap)
+
+    def texture_finalize(self, acc_ptr, W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x, overlap, out_u8, b_grey, out_ptr):
+        call("ghm_texture_finalize", self.h, C.c_void_p(int(acc_ptr)), W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x,
+             overlap, int(out_u8), int(b_grey), C.c_void_p(int(out_ptr)))
 
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous

@@ -118,6 +118,18 @@ class Pix2Pix:
         self.z_fn = lambda Z: eng.generate('dcgan_gen', Z, False)
         self.z_fn_det = lambda Z: eng.generate('dcgan_gen', Z, True)
 
+    def texture_heightmap(self, heightmap, overlap=None, batch_size=4, out=None, uint8=False, deterministic=True):
+        """Texture a heightmap of any size: overlapping in_shp x in_shp tiles through gen_fn_det's forward plan, the overlaps
+        cross-faded (gan_heightmaps_amd/texture.py).  Not in the reference.
+        heightmap: (H, W) or (H, W, C_a) uint8 (normalised as the training path does), or (C_a, H, W) float32 already
+        normalised; any array that slices by rows (np.memmap, an HDF5 dataset) works.  overlap: tile overlap in pixels,
+        0 .. in_shp / 2 (default in_shp / 4).  Returns (C_out, H, W) float32, or with uint8=True the (H, W, 3) uint8 RGB
+        of util.to_uint8(util.convert_to_rgb(.)); ``out`` (that shape and dtype) is written in place of a new array.
+        Leaves the training state untouched."""
+        from .texture import texture_heightmap
+        return texture_heightmap(self.engine, heightmap, self.is_a_grayscale, self.is_b_grayscale, overlap=overlap,
+                                 batch_size=batch_size, out=out, uint8=uint8, deterministic=deterministic)
+
     def _is_writer(self):
         """files (results.txt, PNG dumps, checkpoints) are written by rank 0 only; every rank still runs the
         forward passes and iterator draws of the per-epoch dumps, which are part of the training trajectory"""
