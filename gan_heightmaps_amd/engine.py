@@ -290,7 +290,9 @@ def _rewrite(out_node, dtype='f32'):
                     # R3b: BilinearUpsample2DLayer(2) -> 3x3 'same' conv (p2p.py:204-267) the same way: a packed 3x3 conv with
                     # 4K filters on the coarse input (25 of its 36 collapsed taps non-zero) + the frame Theano's border
                     # handling adds (csrc/conv_bilinear.hip); mode 1 of the same node
-                    if not _blconv_wanted(l, n.inputs[0].layer, dtype):
+                    # (the frame kernels add Theano's border lines to the linear product: a nonlinearity of the conv's own,
+                    # folded by R2 or not, keeps the literal form)
+                    if n.act != linear or not _blconv_wanted(l, n.inputs[0].layer, dtype):
                         continue
                     mode = 1
                 uc = Node('upconv', [n.inputs[0].inputs[0]], l, mode=mode)
@@ -516,7 +518,7 @@ class NetPlan:
                 d = self._upconv_desc(n, n.inputs[0].out)
             else:
                 continue
-            if self._lp(d, 0) and n.inputs[0].shape[1] % 8 == 0:
+            if self._lp(d, 0) and n.inputs[0].shape[1] % 8 == 0 and self._q_viewable(n.inputs[0]):
                 need.append(n.inputs[0])
 
         def get_outq(n):
@@ -537,6 +539,22 @@ class NetPlan:
                 for i in n.inputs:
                     if i.alias is not None and i.alias[0] is n:
                         get_outq(i)
+                        if i.op == 'input':     # no kernel writes a net input: its q slice is packed by the forward
+                            i.aux['q_whole'] = True
+
+    @staticmethod
+    def _q_viewable(n):
+        """can the q copy of n exist?  A concat's is written through its members' slices, each of which must start and
+        end on a multiple of 8 channels (else the convolution that reads it takes the fp32 tensor, as for any input whose
+        channel count is not a multiple of 8)"""
+        if n.op != 'concat':
+            return True
+        c0 = 0
+        for i in n.inputs:
+            if c0 % 8 or i.shape[1] % 8:
+                return False
+            c0 += i.shape[1]
+        return True
 
     def _wq(self, d):
         """is the weight gradient of this convolution the q-operand kernel (lp_wgrad_q: 3x3 stride 1 / 2, 5x5 stride 1)?

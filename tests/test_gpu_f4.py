@@ -61,63 +61,41 @@ def _variant(name):
 @pytest.mark.parametrize("name", ["g_unet_256", "discriminator2", "patchgan_num_repeats", "unet_num_repeats",
                                   "dcgan_gen_num_repeats", "dcgan_disc_num_repeats_avgpool", "dcgan_disc_avgpool"])
 def test_architecture_variant_on_the_device(gpu, name):
-    import symtheano as ST
-    from oracle import tape as TP
+    from tests import lowering_corpus as LC
     from gan_heightmaps_amd import init as INIT, layers as L
-    from gan_heightmaps_amd.engine import NetPlan, ParamStore
     dev, ops = gpu
     INIT.set_rng(np.random.RandomState(11))
     net, in_layers, feeds = _variant(name)
     if in_layers is None:
         in_layers = [l for l in L.get_all_layers(net) if isinstance(l, L.InputLayer)]
         feeds = {0: feeds[None]}
-    B = feeds[0].shape[0]
-    store = ParamStore(dev, L.get_all_params(net))
-    plan = NetPlan(dev, ops, net, B, store, name=name)
-    fwd, bwd = [], []
-    plan.emit_forward(fwd)
-    seed = np.random.RandomState(2).randn(*plan.out.shape).astype(np.float32)
-    seed_d = dev.tensor(seed)
-    want_in = [l for l in in_layers if len(l.shape) == 4]          # image inputs: their gradient is checked too
-    gin = plan.emit_backward(bwd, seed_d, input_grads=want_in)
-    for i, l in enumerate(in_layers):
-        t = plan.input_tensor(l)
-        t.set(np.asarray(feeds[i], np.float32).reshape(t.shape))
-    for e in fwd + bwd:
-        e[1]()
-    dev.sync()
+    g = LC.Graph(name, net, in_layers, [feeds[i] for i in range(len(in_layers))])
+    res = LC.run_on_device(dev, ops, g)              # forward + backward (image-input gradients), then the deterministic pass
     # ---- the same graph on the oracle's ops, float64 ----
-    env = {"in%d" % i: np.asarray(feeds[i], np.float32) for i in range(len(in_layers))}
-    c = ST.Ctx(env, np.float64)
-    sym_in = {l: ST.placeholder("in%d" % i) for i, l in enumerate(in_layers)}
-    ref = ST.get_output(net, sym_in).ev(c)
-    assert rel(plan.out.numpy().reshape(ref.v.shape), ref.v) < 1e-5, name
-    TP.backward(ref, seed.astype(np.float64).reshape(ref.v.shape))
+    ref = LC.reference(g, res["seed"], res["keys"])
+    assert rel(res["out"].reshape(ref["out"].shape), ref["out"]) < 1e-5, name
     checked = 0
     for p in L.get_all_params(net, trainable=True):
-        g_ref = c.param(p).g
+        g_ref = ref["grads"][id(p)]
         if g_ref is None or np.linalg.norm(g_ref) < 1e-9:
             continue                       # e.g. a conv bias that feeds a BatchNorm: exactly zero
-        assert rel(store.download_grad(p), g_ref) < 5e-4, (name, p.name, p.shape)
+        assert rel(res["grads"][id(p)], g_ref) < 5e-4, (name, p.name, p.shape)
         checked += 1
     assert checked >= 4, name
-    for i, l in enumerate(in_layers):
-        if l in want_in:
-            g_ref = sym_in[l].ev(c).g
-            assert g_ref is not None and np.linalg.norm(g_ref) > 0
-            assert rel(gin[l].numpy(), g_ref) < 5e-4, (name, "input", i)
+    for i, l in enumerate(LC.image_inputs(g)):
+        g_ref = ref["gin"][id(l)]
+        assert g_ref is not None and np.linalg.norm(g_ref) > 0
+        assert rel(res["gin"][id(l)], g_ref) < 5e-4, (name, "input", i)
     # BatchNorm running statistics took the lasagne update (alpha 0.1) from the batch statistics
-    for l, mu, inv in c.bn:
-        assert rel(l.mean.get_value(), 0.9 * 0.0 + 0.1 * mu.ravel()) < 1e-4 or np.abs(mu).max() < 1e-6, name
-        assert rel(l.inv_std.get_value(), 0.9 * 1.0 + 0.1 * inv.ravel()) < 1e-4, name
+    for l in L.get_all_layers(net):
+        if isinstance(l, L.BatchNormLayer):
+            mu, inv = ref["stats"][id(l)]
+            rm, ri = res["running"][id(l)]
+            assert rel(rm, 0.9 * 0.0 + 0.1 * mu.ravel()) < 1e-4 or np.abs(mu).max() < 1e-6, name
+            assert rel(ri, 0.9 * 1.0 + 0.1 * inv.ravel()) < 1e-4, name
     # deterministic pass (gen_fn_det / z_fn_det path): running statistics instead of batch statistics
-    det = []
-    plan.emit_forward(det, deterministic=True)
-    for e in det:
-        e[1]()
-    c2 = ST.Ctx(env, np.float64)
-    ref_det = ST.get_output(net, sym_in, deterministic=True).ev(c2)
-    assert rel(plan.out.numpy().reshape(ref_det.v.shape), ref_det.v) < 1e-5, name
+    ref_det = LC.reference_det(g)
+    assert rel(res["det"].reshape(ref_det.shape), ref_det) < 1e-5, name
 
 
 def _instance_norm_net(kind):
