@@ -1015,6 +1015,19 @@ class Ops:
         call("ghm_texture_finalize", self.h, C.c_void_p(int(acc_ptr)), W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x,
              overlap, int(out_u8), int(b_grey), C.c_void_p(int(out_ptr)))
 
+    # heightmaps of any size (csrc/terrain.hip, gan_heightmaps_amd/terrain.py)
+    def terrain_seed(self, P, gy, gx, s, row0, rows, blend, dst):
+        """canvas seed rows [row0, row0 + rows) of the per-cell maps P [gy gx, C s s] -> dst [1, C, rows, s gx]"""
+        C = dst.Cc
+        assert P.N == gy * gx and P.Cc * P.HW == C * s * s and dst.N == 1 and dst.H == rows and dst.W == s * gx
+        call("ghm_terrain_seed", self.h, _vp(P), P.nstride, gy, gx, C, s, row0, rows, int(blend), _vp(dst), dst.nstride)
+
+    def terrain_emit(self, src, r0, n, out_u8, grey, out_ptr):
+        """rows [r0, r0 + n) of src [1, C, H, W] -> fp32 [C, n, W] or uint8 [n, W] / [n, W, 3] at out_ptr"""
+        assert src.N == 1
+        call("ghm_terrain_emit", self.h, _vp(src), src.Cc, src.H, src.W, r0, n, int(out_u8), int(grey),
+             C.c_void_p(int(out_ptr)))
+
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous
         call("ghm_lsgan_loss", self.h, _vp(d), d.size, target, _vp(loss_out), _vp(grad), grad_scale,

@@ -364,3 +364,26 @@ def set_all_param_values(layer, values, **tags):
 
 def get_output_shape(layer):
     return layer.output_shape
+
+
+def clone_chain(out_layer, after, incoming):
+    """Copies of the single chain of layers from just after ``after`` up to ``out_layer``, re-rooted on ``incoming`` (a
+    layer or a shape tuple).  Every copy shares its Param objects with its original, so a graph built this way reads and
+    trains the same parameters (and lowers onto the same engine.ParamStore).  -> the copy of ``out_layer``."""
+    import copy
+    chain, l = [], out_layer
+    while l is not after:
+        if l is None or isinstance(l, (MergeLayer, InputLayer)):
+            raise ValueError("%r is not on a single-input chain above %r" % (out_layer, after))
+        chain.append(l)
+        l = l.input_layer
+    prev = incoming
+    for l in reversed(chain):
+        c = copy.copy(l)
+        c.params = list(l.params)
+        if isinstance(prev, tuple):
+            c.input_layer, c.input_shape = None, prev
+        else:
+            c.input_layer, c.input_shape = prev, prev.output_shape
+        prev = c
+    return prev

@@ -130,6 +130,20 @@ class Pix2Pix:
         return texture_heightmap(self.engine, heightmap, self.is_a_grayscale, self.is_b_grayscale, overlap=overlap,
                                  batch_size=batch_size, out=out, uint8=uint8, deterministic=deterministic)
 
+    def generate_terrain(self, grid=None, z=None, blend='bilinear', band=None, out=None, uint8=False, deterministic=True):
+        """One seamless heightmap of gy x gx generator outputs from a grid of latent vectors: the DCGAN generator's head
+        runs per cell, the cells' seed maps form one canvas ('mosaic', or 'bilinear' blending between neighbouring cells),
+        and the fully convolutional trunk runs over the canvas in row windows with an exact halo
+        (gan_heightmaps_amd/terrain.py).  Not in the reference.
+        grid=(gy, gx) draws z from ``self.sampler`` (numpy's global RNG, like generate_gz); or give z [gy, gx, latent_dim].
+        band: seed rows kept per window (default: a fixed memory budget).  Returns (C_a, in_shp gy, in_shp gx) float32, or
+        with uint8=True util.to_uint8(util.convert_to_rgb(.)) as (H, W) for a greyscale generator, (H, W, 3) otherwise;
+        ``out`` (that shape and dtype, e.g. an open_memmap) is written in place of a new array.  Leaves the training state
+        untouched."""
+        from .terrain import generate_terrain
+        return generate_terrain(self.engine, self.dcgan['gen'], self.latent_dim, self.sampler, self.is_a_grayscale,
+                                grid=grid, z=z, blend=blend, band=band, out=out, uint8=uint8, deterministic=deterministic)
+
     def _is_writer(self):
         """files (results.txt, PNG dumps, checkpoints) are written by rank 0 only; every rank still runs the
         forward passes and iterator draws of the per-epoch dumps, which are part of the training trajectory"""

@@ -201,6 +201,7 @@ class GanStep:
         self.losses_dev = dev.zeros((1, 8, 1, 1))
         self._built = {}
         self._infer = {}
+        self._subgraph = {}
 
     def loss_scale_state(self):
         """[{scale, clean_steps, skipped_steps}] per stage stream (fp16 mode; [] otherwise).  Synchronises."""
@@ -1104,6 +1105,20 @@ class GanStep:
             self._infer[k] = (plan, prog)
             self._apply_pending_counters()
         return self._infer[k]
+
+    def _subgraph_plan(self, key, tag, B, build):
+        """deterministic forward-only plan of a graph that shares net ``key``'s parameters (terrain.py: the DCGAN generator's
+        head, and its trunk re-rooted on a seed canvas); ``build()`` makes the graph's output layer.  Cached per (key, tag, B)
+        like _infer_plan, so loading a model or training a step is visible to the next run with nothing re-uploaded."""
+        k = (key, tag, B)
+        if k not in self._subgraph:
+            lane = LANE_OF[key]
+            plan = NetPlan(self.devs[lane], self.ops[lane], build(), B, self.stores[key], name="%s_%s" % (key, tag[0]),
+                           dtype=self.dtype)
+            prog = []
+            plan.emit_forward(prog, deterministic=True)
+            self._subgraph[k] = (plan, prog)
+        return self._subgraph[k]
 
     def generate(self, key, inp, deterministic=False):
         inp = np.ascontiguousarray(inp, np.float32)
