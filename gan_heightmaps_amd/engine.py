@@ -24,6 +24,9 @@ from .device import SPLITS, DevTensor, QTensor, conv_desc, pack_conv_w, unpack_c
 from .nonlinearities import linear
 
 ALIGN = 64      # elements; keeps every parameter 256-B aligned inside the flat buffers
+# ``kind`` of a convolution launch (conv_meta, Ops.conv_variant* / lp_supported / lp_q_direct): forward, data gradient,
+# weight gradient, data gradient as a forward-form product on the transposed weights
+FWD, DGRAD, WGRAD, DGRAD_T = 0, 1, 2, 3
 
 
 def _align(n):
@@ -126,6 +129,7 @@ class Node:
         self.out = None
         self.alias = None               # (concat node, channel offset)
         self.aux = {}
+        self.instance = False           # a 'bn' node whose statistics are per instance (InstanceNormLayer)
 
     def __repr__(self):
         return "<%s %s act=%s>" % (self.op, self.shape, self.act.kind)
@@ -312,6 +316,15 @@ def _rewrite(out_node, dtype='f32'):
     return out_node
 
 
+class _ForwardCtx:
+    """what the per-op forward lowerings (NetPlan._fwd_*) share while one forward program is emitted"""
+
+    def __init__(self, prog, deterministic, update_running, lp_done):
+        self.prog, self.deterministic, self.update_running, self.lp_done = prog, deterministic, update_running, lp_done
+        self.fused_hi = set()           # pp_to_hi nodes whose output the BatchNorm in front of them writes
+        self.fused_bn = set()           # BatchNorm nodes that ran inside the finishing kernel of the convolution in front of them
+
+
 class NetPlan:
     """One network lowered for a fixed batch size: buffers + emitters of forward/backward programs."""
 
@@ -347,6 +360,8 @@ class NetPlan:
         if self.use_q:
             self._place_q()
         self._scratch = {}
+        self._collapse_tab = None       # device table of the batched weight collapse (made by the first emit_forward)
+        self._last_grads = {}           # {id(node): gradient buffer} of the last emit_backward (grads_of)
         self.bn_ws = None
         cmax = max([n.shape[1] for n in self.order if n.op == 'bn'] + [0])
         if cmax:
@@ -381,7 +396,7 @@ class NetPlan:
             else:
                 continue
             T = d.kh * d.kw
-            for transposed, kind in ((False, 0), (True, 1)):
+            for transposed, kind in ((False, FWD), (True, DGRAD)):
                 if self._lp(d, kind) and (key, transposed) not in self._lp_wq:
                     wq = self.store.lp_pack((key, transposed, self.dtype), self.ops.lp_weight_bytes(d, transposed, self.dtype))
                     self._lp_wq[(key, transposed)] = wq
@@ -480,7 +495,7 @@ class NetPlan:
 
         for n in self.order:
             get_out(n)
-            if n.op == 'bn' and getattr(n, 'instance', False):
+            if n.op == 'bn' and n.instance:
                 # one instance = one sample; the four parity planes of one image behind a collapsed up-sample convolution
                 grp = 4 if n.inputs[0].op == 'upconv' else 1
                 n.aux['group'] = grp
@@ -518,7 +533,7 @@ class NetPlan:
                 d = self._upconv_desc(n, n.inputs[0].out)
             else:
                 continue
-            if self._lp(d, 0) and n.inputs[0].shape[1] % 8 == 0 and self._q_viewable(n.inputs[0]):
+            if self._lp(d, FWD) and n.inputs[0].shape[1] % 8 == 0 and self._q_viewable(n.inputs[0]):
                 need.append(n.inputs[0])
 
         def get_outq(n):
@@ -576,7 +591,7 @@ class NetPlan:
                 d = self._upconv_desc(c, n.out)
             else:
                 return True
-            if not (self._lp(d, 0) and self._wq(d)):
+            if not (self._lp(d, FWD) and self._wq(d)):
                 return True
         return False
 
@@ -654,7 +669,7 @@ class NetPlan:
         thin fan-out kernel serves them: their reduction is element-wise work (smallk_dgrad_kernel)"""
         if W.shape[1] <= 4 or not self.ops.dgrad_t_supported(d):
             return False
-        return d.K > 4 or self.ops.conv_variant(d, 3).startswith("fanout_kernel")
+        return d.K > 4 or self.ops.conv_variant(d, DGRAD_T).startswith("fanout_kernel")
 
     def _lp(self, d, kind):
         return self.dtype != 'f32' and self.ops.lp_supported(d, kind, self.dtype)
@@ -681,9 +696,9 @@ class NetPlan:
                 or os.environ.get("GHM_NO_CONV_BN_FUSE") is not None or not hasattr(self.ops, 'conv_bn_fused_supported')):
             return None
         bnn = n.consumers[0]
-        if bnn.op != 'bn' or getattr(bnn, 'instance', False) or self._bn_hi(bnn) or n.out.nstride != d.y_nstride:
+        if bnn.op != 'bn' or bnn.instance or self._bn_hi(bnn) or n.out.nstride != d.y_nstride:
             return None
-        if self._lp(d, 0):
+        if self._lp(d, FWD):
             return bnn if (xq is not None and self.ops.conv_bn_fused_supported(d, self.dtype)) else None
         # fp32 product (ghm_conv2d_bn_fwd: the generic gather kernel in split-K form + the same finishing kernel).  Built,
         # parity-tested, and NOT the default: in the fp32 step it measured 169.4 img/s against 171.5 for the split-K
@@ -695,13 +710,13 @@ class NetPlan:
     def _bn_hi(self, n):
         """is n the BatchNorm of a collapsed up-sample convolution whose only reader is the parity interleave?  Then the
         two run as one pass in both directions (csrc/elementwise_q.hip: bn_apply_hi / bn_backward_hi)."""
-        return (n.op == 'bn' and self.bn_groups == 1 and not getattr(n, 'instance', False) and os.environ.get("GHM_NO_BN_HI") is None
+        return (n.op == 'bn' and self.bn_groups == 1 and not n.instance and os.environ.get("GHM_NO_BN_HI") is None
                 and len(n.consumers) == 1 and n.consumers[0].op == 'pp_to_hi' and n.inputs[0].op == 'upconv'
                 and n.shape[1] % 8 == 0 and n.consumers[0].out.nstride % 2 == 0)
 
     def _need_wgrad_ws(self, d):
         b = self.ops.wgrad_workspace(d)
-        if self._lp(d, 2) or self._wq(d):
+        if self._lp(d, WGRAD) or self._wq(d):
             b = max(b, self.ops.wgrad_lp_workspace(d))
         self._grow_wgrad_ws(b)
 
@@ -725,234 +740,272 @@ class NetPlan:
         # (per layer it was two small launches in front of each of the generator's first, latency-bound stages)
         ups = [n for n in self.order if n.op == 'upconv']
         if ups:
-            if getattr(self, '_collapse_tab', None) is None:
+            if self._collapse_tab is None:
                 self._collapse_tab = ops.collapse_table(
                     [(st.value(n.layer.W), st.value(n.layer.b), n.aux['wpc'], n.aux['b4'], n.inputs[0].shape[1], n.shape[1],
                       n.attrs.get('mode', 0)) for n in ups])
             prog.append(("collapse_w", lambda t=self._collapse_tab: ops.upconv_collapse_batched(t)))
         if self._lp_table is not None:
             prog.append(("lp_pack", lambda t=self._lp_table: ops.lp_pack_batched(t, self.dtype)))
-        qpack = lambda t, q: prog.append(("q_pack", lambda t=t, q=q: ops.q_pack(t, q), pack_meta(t)))
-        fused_hi = set()            # pp_to_hi nodes whose output the BatchNorm in front of them writes
-        fused_bn = set()            # BatchNorm nodes that ran inside the finishing kernel of the convolution in front of them
+        ctx = _ForwardCtx(prog, deterministic, update_running, lp_done)
         for n in self.order:
-            if id(n) in fused_bn:
+            if id(n) in ctx.fused_bn:
                 continue
-            y = n.out
-            if n.op in ('input', 'reshape', 'concat'):
-                if n.op == 'concat':
-                    c0 = 0
-                    for i in n.inputs:
-                        if i.alias is None or i.alias[0] is not n:
-                            dst = y.channels(c0, c0 + i.shape[1])
-                            prog.append(("concat_copy", lambda a=i.out, b=dst: ops.copy_view(a, b)))
-                            if n.aux.get('q_whole'):
-                                qpack(dst, n.outq.channels(c0, c0 + i.shape[1]))
-                        elif n.aux.get('q_whole'):
-                            if i.outq is None or i.outq.base is not (n.outq.base if n.outq.base is not None else n.outq):
-                                raise NotImplementedError("ConcatLayer input at a channel offset that is not a multiple "
-                                                          "of 8 feeding a low-precision convolution")
-                        c0 += i.shape[1]
-                elif n.aux.get('q_whole'):      # a net input / reshaped tensor that a low-precision product reads
-                    qpack(y, n.outq)
-                continue
-            x = n.inputs[0].out
-            xq = n.inputs[0].outq
-            q_direct = False                # did the node's own kernel write n.outq?
-            a = n.act
-            if n.op in ('conv', 'dense'):
-                d = self._desc(n, x, y)
-                w, b = st.value(n.layer.W), st.value(n.layer.b)
-                bnn = self._conv_bn_fusable(n, d, xq, deterministic)
-                if bnn is not None:
-                    # small maps: Conv2DLayer -> BatchNormLayer (-> nonlinearity) as ONE product -- the finishing kernel of
-                    # the convolution holds the whole map of its channels (csrc/conv_small.hip)
-                    lb = bnn.layer
-                    fused_bn.add(id(bnn))
-                    y32 = bnn.out if (bnn.outq is None or self._fp32_needed(bnn)) else None
-                    rm, ri = (st.value(lb.mean), st.value(lb.inv_std)) if update_running else (None, None)
-                    if not self._lp(d, 0):
-                        prog.append(("conv_bn_fwd", lambda d=d, x=x, w=w, b=b, co=y, y32=bnn.out, lb=lb, rm=rm, ri=ri,
-                                     m=bnn.aux['mean'], iv=bnn.aux['inv'], ba=bnn.act:
-                                     ops.conv2d_bn_fwd(d, x, w, b, co, y32, st.value(lb.gamma), st.value(lb.beta), m, iv, rm, ri,
-                                                       lb.epsilon, lb.alpha, ba.kind, ba.alpha), conv_meta(ops, d, 0)))
-                        continue
-                    wq = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, lp_done)
-                    prog.append(("conv_bn_fwd", lambda d=d, xq=xq, wq=wq, b=b, co=y, y32=y32, yq=bnn.outq, lb=lb, rm=rm, ri=ri,
-                                 m=bnn.aux['mean'], iv=bnn.aux['inv'], ba=bnn.act:
-                                 ops.conv2d_bn_fwd_lp_q(d, xq, wq, b, co, y32, yq, st.value(lb.gamma), st.value(lb.beta), m, iv,
-                                                        rm, ri, lb.epsilon, lb.alpha, self.dtype, ba.kind, ba.alpha),
-                                 conv_meta(ops, d, 0, self.dtype)))
-                elif n.op == 'conv' and self._lp(d, 0):
-                    wq = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, lp_done)
-                    if xq is not None:
-                        q_direct = n.outq is not None and ops.lp_q_direct(d, 0, self.dtype)
-                        yq = n.outq if q_direct else None
-                        y32 = None if (q_direct and self._act_fp32_dropped(n)) else y
-                        prog.append(("conv_fwd", lambda d=d, xq=xq, wq=wq, b=b, y=y32, yq=yq, a=a:
-                                     ops.conv2d_fwd_lp_q(d, xq, wq, b, y, yq, self.dtype, a.kind, a.alpha),
-                                     conv_meta(ops, d, 0, self.dtype)))
-                    else:
-                        prog.append(("conv_fwd", lambda d=d, x=x, wq=wq, b=b, y=y, a=a:
-                                     ops.conv2d_fwd_lp(d, x, wq, b, y, self.dtype, a.kind, a.alpha),
-                                     conv_meta(ops, d, 0, self.dtype)))
-                elif n.op == 'conv' and n.outq is not None and ops.thin_fwd_q_supported(d, a.kind, False, self.dtype):
-                    q_direct = True         # a first layer (fp32 operands) whose epilogue also writes the q copy
-                    y32 = None if self._act_fp32_dropped(n) else y
-                    prog.append(("conv_fwd", lambda d=d, x=x, w=w, b=b, y=y32, yq=n.outq, a=a:
-                                 ops.conv2d_fwd_thin_q(d, x, w, b, y, yq, a.kind, a.alpha),
-                                 conv_meta(ops, d, 0, moved=4.0 * d.N * d.C * d.H * d.W
-                                           + ((0.0 if y32 is None else 4.0) + self._q_bytes()) * d.N * d.K * d.Ho * d.Wo)))
-                else:
-                    prog.append(("%s_fwd" % n.op, lambda d=d, x=x, w=w, b=b, y=y, a=a:
-                                 ops.conv2d_fwd(d, x, w, b, y, a.kind, a.alpha), conv_meta(ops, d, 0)))
-            elif n.op == 'convpool':
-                d = self._desc(n, x, self._full(n))
-                w, b = st.value(n.layer.W), st.value(n.layer.b)
-                form = ops.conv_pool_supported(d, a.kind, self.dtype)
-                assert form in (1, 2), "fused conv + pool no longer served for %r" % (n,)
-                wsrc, dt = w, 'f32'
-                if form == 2:
-                    wsrc, dt = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, lp_done), self.dtype
-                if self._pool_y_dropped(n):
-                    y = None                # (pooled fp32 tensor not written: see _pool_y_dropped)
-                if form == 2 and xq is not None:
-                    q_direct = n.outq is not None
-                    prog.append(("convpool_fwd", lambda d=d, xq=xq, wsrc=wsrc, b=b, y=y, yq=n.outq, m=n.aux['mask'], a=a:
-                                 ops.conv2d_fwd_pool_lp_q(d, xq, wsrc, b, y, yq, m, a.kind, a.alpha, self.dtype),
-                                 conv_meta(ops, d, 0, dt, pooled=True)))
-                elif form == 1 and n.outq is not None and ops.thin_fwd_q_supported(d, a.kind, True, self.dtype):
-                    q_direct = True
-                    prog.append(("convpool_fwd", lambda d=d, x=x, w=w, b=b, y=y, yq=n.outq, m=n.aux['mask'], a=a:
-                                 ops.conv2d_fwd_pool_thin_q(d, x, w, b, y, m, yq, a.kind, a.alpha),
-                                 conv_meta(ops, d, 0, 'f32', pooled=True,
-                                           moved=4.0 * d.N * d.C * d.H * d.W + ((0.0 if y is None else 4.0) + 1.0 + self._q_bytes())
-                                           * d.N * d.K * (d.Ho // 2) * (d.Wo // 2))))
-                else:
-                    prog.append(("convpool_fwd", lambda d=d, x=x, wsrc=wsrc, b=b, y=y, m=n.aux['mask'], a=a, dt=dt:
-                                 ops.conv2d_fwd_pool(d, x, wsrc, b, y, m, a.kind, a.alpha, dt),
-                                 conv_meta(ops, d, 0, dt, pooled=True)))
-            elif n.op == 'deconv':
-                d = self._desc(n, y, x)
-                w, b = st.value(n.layer.W), st.value(n.layer.b)
-                prog.append(("deconv_fwd", lambda d=d, x=x, w=w, b=b, y=y, a=a:
-                             ops.conv2d_dgrad(d, x, w, y, b, a.kind, a.alpha), conv_meta(ops, d, 1)))
-            elif n.op == 'bn' and getattr(n, 'instance', False):
-                l = n.layer
-                g, be = st.value(l.gamma), st.value(l.beta)
-                prog.append(("in_fwd", lambda x=x, y=y, m=n.aux['mean'], iv=n.aux['inv'], g=g, be=be, l=l, a=a, grp=n.aux['group']:
-                             ops.instance_norm_fwd(x, y, m, iv, g, be, self.bn_ws, l.epsilon, a.kind, a.alpha, grp)))
-            elif n.op == 'bn':
-                l = n.layer
-                g, be = st.value(l.gamma), st.value(l.beta)
-                rm, ri = st.value(l.mean), st.value(l.inv_std)
-                if deterministic:
-                    prog.append(("bn_apply_det", lambda x=x, y=y, rm=rm, ri=ri, g=g, be=be, a=a:
-                                 ops.bn_apply(x, y, rm, ri, g, be, a.kind, a.alpha)))
-                elif self.bn_groups == 2:
-                    # per-half statistics; the running statistics take the update of the SECOND half only: Lasagne
-                    # attaches one default_update per get_output call to the same storage, both computed from the
-                    # old value, so one of them survives (unspecified which; the later call is assumed here)
-                    hb = x.N // 2
-                    for h in (0, 1):
-                        xs, ys = x.samples(h * hb, (h + 1) * hb), y.samples(h * hb, (h + 1) * hb)
-                        m, iv = n.aux['mean_g'][h], n.aux['inv_g'][h]
-                        upd = update_running and h == 1
-                        prog.append(("bn_fwd", lambda xs=xs, ys=ys, m=m, iv=iv, rm=rm, ri=ri, l=l, upd=upd, g=g, be=be, a=a:
-                                     ops.bn_forward(xs, ys, m, iv, g, be, self.bn_ws, rm if upd else None,
-                                                    ri if upd else None, l.epsilon, l.alpha, a.kind, a.alpha)))
-                elif self._bn_hi(n):
-                    # BatchNorm of a collapsed up-sample convolution: statistics, then normalise + activation written
-                    # straight in the interleaved layout of the pp_to_hi node behind it (fp32 and / or q); the parity-planar
-                    # result is never stored (the backward pass recomputes it from x)
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    upd = update_running
-                    sh = n.consumers[0]
-                    fused_hi.add(id(sh))
-                    hi32 = sh.out if (sh.outq is None or self._fp32_needed(sh)) else None
-                    prog.append(("bn_fwd", lambda x=x, m=m, iv=iv, rm=rm, ri=ri, l=l, upd=upd:
-                                 ops.bn_stats(x, m, iv, self.bn_ws, rm if upd else None, ri if upd else None, l.epsilon, l.alpha)))
-                    prog.append(("bn_fwd", lambda x=x, hi32=hi32, hiq=sh.outq if self.q_epi else None, m=m, iv=iv, g=g, be=be, a=a:
-                                 ops.bn_apply_hi(x, hi32, hiq, m, iv, g, be, a.kind, a.alpha)))
-                elif n.outq is not None and self.q_epi and x.HW % 2 == 0 and x.nstride % 2 == 0 and y.nstride % 2 == 0:
-                    # statistics, then normalise + activation writing the fp32 result AND its q copy in one pass
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    upd = update_running
-                    q_direct = True
-                    prog.append(("bn_fwd", lambda x=x, m=m, iv=iv, rm=rm, ri=ri, l=l, upd=upd:
-                                 ops.bn_stats(x, m, iv, self.bn_ws, rm if upd else None, ri if upd else None, l.epsilon, l.alpha)))
-                    y32 = y if (self._fp32_needed(n) or os.environ.get("GHM_BN_FP32") is not None) else None
-                    prog.append(("bn_fwd", lambda x=x, y32=y32, yq=n.outq, m=m, iv=iv, g=g, be=be, a=a:
-                                 ops.bn_apply_q(x, y32, m, iv, g, be, yq, a.kind, a.alpha)))
-                else:
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    upd = update_running
-                    prog.append(("bn_fwd", lambda x=x, y=y, m=m, iv=iv, rm=rm, ri=ri, l=l, upd=upd, g=g, be=be, a=a:
-                                 ops.bn_forward(x, y, m, iv, g, be, self.bn_ws, rm if upd else None, ri if upd else None,
-                                                l.epsilon, l.alpha, a.kind, a.alpha)))
-            elif n.op == 'upconv':
-                d = self._upconv_desc(n, x)
-                w5, b = st.value(n.layer.W), st.value(n.layer.b)
-                wpc, b4 = n.aux['wpc'], n.aux['b4']
-                C, K = x.Cc, n.shape[1]
-                ulab = 'blconv' if n.attrs.get('mode') == 1 else 'upconv'     # (bench.py prices 'upconv' launches at 25 / 9)
-                y4 = y.reshape((x.N, 4 * K, x.H, x.W))
-                if self._lp(d, 0):
-                    wq = self._lp_pack_entry(prog, d, wpc, ('c', id(n.layer.W)), False, None)    # after collapse_w
-                    if xq is not None and self._bl_skip(n, d, 0) and a == linear:
-                        # the bilinear form's structurally zero taps skipped (25 of 36 k-steps): bit-identical to the full kernel
-                        prog.append((ulab + "_fwd", lambda d=d, xq=xq, wq=wq, b4=b4, y4=y4:
-                                     ops.blconv_fwd_split(d, xq, wq, b4, y4, self.dtype), bl_meta(conv_meta(ops, d, 0, self.dtype))))
-                    elif xq is not None:
-                        prog.append((ulab + "_fwd", lambda d=d, xq=xq, wq=wq, b4=b4, y4=y4, a=a:
-                                     ops.conv2d_fwd_lp_q(d, xq, wq, b4, y4, None, self.dtype, a.kind, a.alpha),
-                                     conv_meta(ops, d, 0, self.dtype)))
-                    else:
-                        prog.append((ulab + "_fwd", lambda d=d, x=x, wq=wq, b4=b4, y4=y4, a=a:
-                                     ops.conv2d_fwd_lp(d, x, wq, b4, y4, self.dtype, a.kind, a.alpha),
-                                     conv_meta(ops, d, 0, self.dtype)))
-                else:
-                    prog.append((ulab + "_fwd", lambda d=d, x=x, wpc=wpc, b4=b4, y4=y4, a=a:
-                                 ops.conv2d_fwd(d, x, wpc, b4, y4, a.kind, a.alpha), conv_meta(ops, d, 0)))
-                if n.attrs.get('mode') == 1:
-                    if a != linear:
-                        raise NotImplementedError("bilinear up-sample convolution with its own nonlinearity")
-                    # what the zero-extended coarse convolution leaves out: Theano's border rows / columns (conv_bilinear.hip)
-                    prog.append(("blconv_frame_fwd", lambda x=x, w5=w5, y4=y4, K=K, fl=n.aux['fl']: ops.blconv_frame_fwd(x, w5, y4, K, fl)))
-            elif n.op == 'pp_to_hi':
-                if id(n) in fused_hi:
-                    q_direct = self.q_epi                          # written by the BatchNorm in front of it
-                elif n.outq is not None and self.q_epi and y.nstride % 2 == 0:
-                    q_direct = True
-                    y32 = y if self._fp32_needed(n) else None      # every consumer reads the q copy: no fp32 tensor
-                    prog.append(("pp_to_hi", lambda x=x, y32=y32, yq=n.outq: ops.pp_to_hi_q(x, y32, yq)))
-                else:
-                    prog.append(("pp_to_hi", lambda x=x, y=y: ops.pp_to_hi(x, y)))
-            elif n.op == 'dropout':
-                if deterministic:
-                    prog.append(("dropout_det", lambda x=x, y=y: ops.copy_view(x, y)))
-                else:
-                    prog.append(("dropout_fwd", lambda x=x, y=y, p=n.attrs['p'], k=n.aux['key'], c=self.rng_counter:
-                                 ops.dropout(x, y, p, k, c)))
-            elif n.op == 'act':
-                prog.append(("act_fwd", lambda x=x, y=y, a=a: ops.act_fwd(x, y, a.kind, a.alpha)))
-            elif n.op == 'up_nearest':
-                prog.append(("up_nearest_fwd", lambda x=x, y=y: ops.upsample_nearest2_fwd(x, y)))
-            elif n.op == 'up_bilinear':
-                if n.outq is not None and self.q_epi:
-                    q_direct = True
-                    y32 = y if self._fp32_needed(n) else None
-                    prog.append(("up_bilinear_fwd", lambda x=x, y32=y32, yq=n.outq: ops.upsample_bilinear2_fwd_q(x, y32, yq)))
-                else:
-                    prog.append(("up_bilinear_fwd", lambda x=x, y=y: ops.upsample_bilinear2_fwd(x, y)))
-            elif n.op == 'maxpool':
-                prog.append(("maxpool_fwd", lambda x=x, y=y: ops.maxpool2_fwd(x, y)))
-            elif n.op == 'avgpool':
-                prog.append(("avgpool_fwd", lambda x=x, y=y, p=n.attrs['p']: ops.avgpool_fwd(x, y, p)))
-            else:
+            lower = getattr(self, '_fwd_' + n.op, None)
+            if lower is None:
                 raise NotImplementedError(n.op)
+            q_direct = lower(ctx, n)        # did the node's own kernel write n.outq (or is there nothing to pack)?
             if n.outq is not None and not q_direct:
-                qpack(y, n.outq)            # producers without a q epilogue of their own: one extra pass
+                self._q_pack(prog, n.out, n.outq)       # producers without a q epilogue of their own: one extra pass
+
+    # one method per op family: appends the node's launches to ctx.prog, -> True if n.outq needs no separate q_pack pass
+    def _q_pack(self, prog, t, q):
+        ops = self.ops
+        prog.append(("q_pack", lambda: ops.q_pack(t, q), pack_meta(t)))
+
+    def _fwd_placed(self, ctx, n):
+        if n.aux.get('q_whole'):        # a net input / reshaped tensor that a low-precision product reads
+            self._q_pack(ctx.prog, n.out, n.outq)
+        return True
+
+    _fwd_input = _fwd_reshape = _fwd_placed
+
+    def _fwd_concat(self, ctx, n):
+        ops, c0 = self.ops, 0
+        for i in n.inputs:
+            if i.alias is None or i.alias[0] is not n:
+                dst = n.out.channels(c0, c0 + i.shape[1])
+                ctx.prog.append(("concat_copy", lambda a=i.out, b=dst: ops.copy_view(a, b)))
+                if n.aux.get('q_whole'):
+                    self._q_pack(ctx.prog, dst, n.outq.channels(c0, c0 + i.shape[1]))
+            elif n.aux.get('q_whole'):
+                if i.outq is None or i.outq.base is not (n.outq.base if n.outq.base is not None else n.outq):
+                    raise NotImplementedError("ConcatLayer input at a channel offset that is not a multiple "
+                                              "of 8 feeding a low-precision convolution")
+            c0 += i.shape[1]
+        return True
+
+    def _conv_fwd_entry(self, label, d, x, xq, w, wq, b, y, yq, a):
+        """-> the entry of one forward convolution, by the first form that applies: q operands -> fp32 operands on the
+        low-precision kernel -> the fp32 kernel (``wq``: the low-precision weight pack, None where those kernels do not serve d)"""
+        ops = self.ops
+        if wq is not None and xq is not None:
+            return (label, lambda: ops.conv2d_fwd_lp_q(d, xq, wq, b, y, yq, self.dtype, a.kind, a.alpha),
+                    conv_meta(ops, d, FWD, self.dtype))
+        if wq is not None:
+            return (label, lambda: ops.conv2d_fwd_lp(d, x, wq, b, y, self.dtype, a.kind, a.alpha),
+                    conv_meta(ops, d, FWD, self.dtype))
+        return (label, lambda: ops.conv2d_fwd(d, x, w, b, y, a.kind, a.alpha), conv_meta(ops, d, FWD))
+
+    def _bn_running(self, l, upd):
+        """-> the running mean / inverse deviation of BatchNormLayer l for a kernel to update, (None, None) to leave them"""
+        return (self.store.value(l.mean), self.store.value(l.inv_std)) if upd else (None, None)
+
+    def _fwd_conv_dense(self, ctx, n):
+        ops, st, prog = self.ops, self.store, ctx.prog
+        x, xq, y, a = n.inputs[0].out, n.inputs[0].outq, n.out, n.act
+        d = self._desc(n, x, y)
+        w, b = st.value(n.layer.W), st.value(n.layer.b)
+        bnn = self._conv_bn_fusable(n, d, xq, ctx.deterministic)
+        if bnn is not None:
+            return self._fwd_conv_bn(ctx, n, bnn, d, w, b)
+        if n.op == 'conv' and self._lp(d, FWD):
+            wq = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, ctx.lp_done)
+            q_direct, y32, yq = False, y, None
+            if xq is not None:
+                q_direct = n.outq is not None and ops.lp_q_direct(d, FWD, self.dtype)
+                yq = n.outq if q_direct else None
+                y32 = None if (q_direct and self._act_fp32_dropped(n)) else y
+            prog.append(self._conv_fwd_entry("conv_fwd", d, x, xq, w, wq, b, y32, yq, a))
+            return q_direct
+        if n.op == 'conv' and n.outq is not None and ops.thin_fwd_q_supported(d, a.kind, False, self.dtype):
+            # a first layer (fp32 operands) whose epilogue also writes the q copy
+            y32, yq = (None if self._act_fp32_dropped(n) else y), n.outq
+            prog.append(("conv_fwd", lambda: ops.conv2d_fwd_thin_q(d, x, w, b, y32, yq, a.kind, a.alpha),
+                         conv_meta(ops, d, FWD, moved=4.0 * d.N * d.C * d.H * d.W
+                                   + ((0.0 if y32 is None else 4.0) + self._q_bytes()) * d.N * d.K * d.Ho * d.Wo)))
+            return True
+        prog.append(self._conv_fwd_entry("%s_fwd" % n.op, d, x, None, w, None, b, y, None, a))
+        return False
+
+    _fwd_conv = _fwd_dense = _fwd_conv_dense
+
+    def _fwd_conv_bn(self, ctx, n, bnn, d, w, b):
+        """small maps: Conv2DLayer -> BatchNormLayer (-> nonlinearity) as ONE product -- the finishing kernel of the
+        convolution holds the whole map of its channels (csrc/conv_small.hip)"""
+        ops, st, prog = self.ops, self.store, ctx.prog
+        x, xq, y = n.inputs[0].out, n.inputs[0].outq, n.out
+        lb, ba = bnn.layer, bnn.act
+        ctx.fused_bn.add(id(bnn))
+        by, byq = bnn.out, bnn.outq
+        y32 = by if (byq is None or self._fp32_needed(bnn)) else None
+        rm, ri = self._bn_running(lb, ctx.update_running)
+        m, iv = bnn.aux['mean'], bnn.aux['inv']
+        if not self._lp(d, FWD):
+            prog.append(("conv_bn_fwd", lambda: ops.conv2d_bn_fwd(d, x, w, b, y, by, st.value(lb.gamma), st.value(lb.beta),
+                                                                   m, iv, rm, ri, lb.epsilon, lb.alpha, ba.kind, ba.alpha),
+                         conv_meta(ops, d, FWD)))
+            return True
+        wq = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, ctx.lp_done)
+        prog.append(("conv_bn_fwd", lambda: ops.conv2d_bn_fwd_lp_q(d, xq, wq, b, y, y32, byq, st.value(lb.gamma),
+                                                                    st.value(lb.beta), m, iv, rm, ri, lb.epsilon, lb.alpha,
+                                                                    self.dtype, ba.kind, ba.alpha),
+                     conv_meta(ops, d, FWD, self.dtype)))
+        return False
+
+    def _fwd_convpool(self, ctx, n):
+        ops, st, prog = self.ops, self.store, ctx.prog
+        x, xq, y, yq, a, mask = n.inputs[0].out, n.inputs[0].outq, n.out, n.outq, n.act, n.aux['mask']
+        d = self._desc(n, x, self._full(n))
+        w, b = st.value(n.layer.W), st.value(n.layer.b)
+        form = ops.conv_pool_supported(d, a.kind, self.dtype)
+        assert form in (1, 2), "fused conv + pool no longer served for %r" % (n,)
+        wsrc, dt = w, 'f32'
+        if form == 2:
+            wsrc, dt = self._lp_pack_entry(prog, d, w, ('w', id(n.layer.W)), False, ctx.lp_done), self.dtype
+        if self._pool_y_dropped(n):
+            y = None                # (pooled fp32 tensor not written: see _pool_y_dropped)
+        if form == 2 and xq is not None:
+            prog.append(("convpool_fwd", lambda: ops.conv2d_fwd_pool_lp_q(d, xq, wsrc, b, y, yq, mask, a.kind, a.alpha, self.dtype),
+                         conv_meta(ops, d, FWD, dt, pooled=True)))
+            return yq is not None
+        if form == 1 and yq is not None and ops.thin_fwd_q_supported(d, a.kind, True, self.dtype):
+            prog.append(("convpool_fwd", lambda: ops.conv2d_fwd_pool_thin_q(d, x, w, b, y, mask, yq, a.kind, a.alpha),
+                         conv_meta(ops, d, FWD, 'f32', pooled=True,
+                                   moved=4.0 * d.N * d.C * d.H * d.W + ((0.0 if y is None else 4.0) + 1.0 + self._q_bytes())
+                                   * d.N * d.K * (d.Ho // 2) * (d.Wo // 2))))
+            return True
+        prog.append(("convpool_fwd", lambda: ops.conv2d_fwd_pool(d, x, wsrc, b, y, mask, a.kind, a.alpha, dt),
+                     conv_meta(ops, d, FWD, dt, pooled=True)))
+        return False
+
+    def _fwd_deconv(self, ctx, n):
+        ops, st = self.ops, self.store
+        x, y, a = n.inputs[0].out, n.out, n.act
+        d = self._desc(n, y, x)
+        w, b = st.value(n.layer.W), st.value(n.layer.b)
+        ctx.prog.append(("deconv_fwd", lambda: ops.conv2d_dgrad(d, x, w, y, b, a.kind, a.alpha), conv_meta(ops, d, DGRAD)))
+        return False
+
+    def _fwd_bn(self, ctx, n):
+        ops, st, prog = self.ops, self.store, ctx.prog
+        x, y, yq, a, l = n.inputs[0].out, n.out, n.outq, n.act, n.layer
+        g, be = st.value(l.gamma), st.value(l.beta)
+        m, iv = n.aux['mean'], n.aux['inv']
+        if n.instance:
+            prog.append(("in_fwd", lambda grp=n.aux['group']:
+                         ops.instance_norm_fwd(x, y, m, iv, g, be, self.bn_ws, l.epsilon, a.kind, a.alpha, grp)))
+            return False
+        if ctx.deterministic:
+            rm, ri = self._bn_running(l, True)
+            prog.append(("bn_apply_det", lambda: ops.bn_apply(x, y, rm, ri, g, be, a.kind, a.alpha)))
+            return False
+        rm, ri = self._bn_running(l, ctx.update_running)
+        if self.bn_groups == 2:
+            # per-half statistics; the running statistics take the update of the SECOND half only: Lasagne
+            # attaches one default_update per get_output call to the same storage, both computed from the
+            # old value, so one of them survives (unspecified which; the later call is assumed here)
+            hb = x.N // 2
+            for h in (0, 1):
+                xs, ys = x.samples(h * hb, (h + 1) * hb), y.samples(h * hb, (h + 1) * hb)
+                rmh, rih = self._bn_running(l, ctx.update_running and h == 1)
+                prog.append(("bn_fwd", lambda xs=xs, ys=ys, m=n.aux['mean_g'][h], iv=n.aux['inv_g'][h], rmh=rmh, rih=rih:
+                             ops.bn_forward(xs, ys, m, iv, g, be, self.bn_ws, rmh, rih, l.epsilon, l.alpha, a.kind, a.alpha)))
+            return False
+        hi, q = self._bn_hi(n), False
+        if not hi:
+            q = yq is not None and self.q_epi and x.HW % 2 == 0 and x.nstride % 2 == 0 and y.nstride % 2 == 0
+        if not (hi or q):
+            prog.append(("bn_fwd", lambda: ops.bn_forward(x, y, m, iv, g, be, self.bn_ws, rm, ri, l.epsilon, l.alpha, a.kind, a.alpha)))
+            return False
+        # two passes: statistics, then normalise + activation with a q epilogue
+        prog.append(("bn_fwd", lambda: ops.bn_stats(x, m, iv, self.bn_ws, rm, ri, l.epsilon, l.alpha)))
+        if hi:
+            # BatchNorm of a collapsed up-sample convolution: written straight in the interleaved layout of the pp_to_hi
+            # node behind it (fp32 and / or q); the parity-planar result is never stored (the backward pass recomputes it from x)
+            sh = n.consumers[0]
+            ctx.fused_hi.add(id(sh))
+            hi32 = sh.out if (sh.outq is None or self._fp32_needed(sh)) else None
+            hiq = sh.outq if self.q_epi else None
+            prog.append(("bn_fwd", lambda: ops.bn_apply_hi(x, hi32, hiq, m, iv, g, be, a.kind, a.alpha)))
+            return False
+        # the fp32 result AND its q copy in one pass
+        y32 = y if (self._fp32_needed(n) or os.environ.get("GHM_BN_FP32") is not None) else None
+        prog.append(("bn_fwd", lambda: ops.bn_apply_q(x, y32, m, iv, g, be, yq, a.kind, a.alpha)))
+        return True
+
+    def _fwd_upconv(self, ctx, n):
+        ops, st, prog = self.ops, self.store, ctx.prog
+        x, xq, y, a = n.inputs[0].out, n.inputs[0].outq, n.out, n.act
+        d = self._upconv_desc(n, x)
+        w5 = st.value(n.layer.W)
+        wpc, b4, K = n.aux['wpc'], n.aux['b4'], n.shape[1]
+        bl = n.attrs.get('mode') == 1
+        label = ('blconv' if bl else 'upconv') + "_fwd"       # (bench.py prices 'upconv' launches at 25 / 9)
+        y4 = y.reshape((x.N, 4 * K, x.H, x.W))
+        wq = None
+        if self._lp(d, FWD):
+            wq = self._lp_pack_entry(prog, d, wpc, ('c', id(n.layer.W)), False, None)    # after collapse_w
+        if wq is not None and xq is not None and self._bl_skip(n, d, FWD) and a == linear:
+            # the bilinear form's structurally zero taps skipped (25 of 36 k-steps): bit-identical to the full kernel
+            prog.append((label, lambda: ops.blconv_fwd_split(d, xq, wq, b4, y4, self.dtype), bl_meta(conv_meta(ops, d, FWD, self.dtype))))
+        else:
+            prog.append(self._conv_fwd_entry(label, d, x, xq, wpc, wq, b4, y4, None, a))
+        if bl:
+            if a != linear:
+                raise NotImplementedError("bilinear up-sample convolution with its own nonlinearity")
+            # what the zero-extended coarse convolution leaves out: Theano's border rows / columns (conv_bilinear.hip)
+            prog.append(("blconv_frame_fwd", lambda fl=n.aux['fl']: ops.blconv_frame_fwd(x, w5, y4, K, fl)))
+        return False
+
+    def _fwd_pp_to_hi(self, ctx, n):
+        ops, x, y, yq = self.ops, n.inputs[0].out, n.out, n.outq
+        if id(n) in ctx.fused_hi:
+            return self.q_epi                              # written by the BatchNorm in front of it
+        if yq is not None and self.q_epi and y.nstride % 2 == 0:
+            y32 = y if self._fp32_needed(n) else None      # every consumer reads the q copy: no fp32 tensor
+            ctx.prog.append(("pp_to_hi", lambda: ops.pp_to_hi_q(x, y32, yq)))
+            return True
+        ctx.prog.append(("pp_to_hi", lambda: ops.pp_to_hi(x, y)))
+        return False
+
+    def _fwd_dropout(self, ctx, n):
+        ops, x, y = self.ops, n.inputs[0].out, n.out
+        if ctx.deterministic:
+            ctx.prog.append(("dropout_det", lambda: ops.copy_view(x, y)))
+        else:
+            ctx.prog.append(("dropout_fwd", lambda p=n.attrs['p'], k=n.aux['key'], c=self.rng_counter: ops.dropout(x, y, p, k, c)))
+        return False
+
+    def _fwd_act(self, ctx, n):
+        ops, x, y, a = self.ops, n.inputs[0].out, n.out, n.act
+        ctx.prog.append(("act_fwd", lambda: ops.act_fwd(x, y, a.kind, a.alpha)))
+        return False
+
+    def _fwd_up_nearest(self, ctx, n):
+        ops, x, y = self.ops, n.inputs[0].out, n.out
+        ctx.prog.append(("up_nearest_fwd", lambda: ops.upsample_nearest2_fwd(x, y)))
+        return False
+
+    def _fwd_up_bilinear(self, ctx, n):
+        ops, x, y, yq = self.ops, n.inputs[0].out, n.out, n.outq
+        if yq is not None and self.q_epi:
+            y32 = y if self._fp32_needed(n) else None
+            ctx.prog.append(("up_bilinear_fwd", lambda: ops.upsample_bilinear2_fwd_q(x, y32, yq)))
+            return True
+        ctx.prog.append(("up_bilinear_fwd", lambda: ops.upsample_bilinear2_fwd(x, y)))
+        return False
+
+    def _fwd_maxpool(self, ctx, n):
+        ops, x, y = self.ops, n.inputs[0].out, n.out
+        ctx.prog.append(("maxpool_fwd", lambda: ops.maxpool2_fwd(x, y)))
+        return False
+
+    def _fwd_avgpool(self, ctx, n):
+        ops, x, y = self.ops, n.inputs[0].out, n.out
+        ctx.prog.append(("avgpool_fwd", lambda p=n.attrs['p']: ops.avgpool_fwd(x, y, p)))
+        return False
+
 
     def emit_transposes(self, prog, transposed):
         """One launch that refreshes every transposed weight copy the data-gradient kernels of this net read
@@ -963,7 +1016,7 @@ class NetPlan:
             if n.op in ('conv', 'convpool'):
                 l = n.layer
                 d = self._desc(n, n.inputs[0].out, self._full(n))
-                if self._lp(d, 1):
+                if self._lp(d, DGRAD):
                     continue                      # its data gradient reads the low-precision transposed pack instead
                 if self._use_dgrad_t(d, l.W) and id(l.W) not in transposed:
                     transposed.add(id(l.W))
@@ -971,7 +1024,7 @@ class NetPlan:
             elif n.op == 'upconv':
                 l = n.layer
                 d = self._upconv_desc(n, n.inputs[0].out)
-                if self._lp(d, 1):
+                if self._lp(d, DGRAD):
                     continue
                 if d.C > 4 and ops.dgrad_t_supported(d) and ('c', id(l.W)) not in transposed:
                     transposed.add(('c', id(l.W)))
@@ -981,8 +1034,8 @@ class NetPlan:
             prog.append(("transpose_w", lambda table=table: ops.transpose_weights_batched(table)))
 
     # ---- backward --------------------------------------------------------------------------------
-    def emit_backward(self, prog, seed, nslice=None, wgrad=True, input_grads=(), accumulate_wgrad=False, tag="bwd",
-                      transposed=None, on_grads=None, resume=None):
+    def emit_backward(self, prog, seed, nslice=None, wgrad=True, input_grads=(), tag="bwd", transposed=None, on_grads=None,
+                      resume=None):
         """Append the backward program.  ``seed``: DevTensor holding dLoss/d(output) (it may be modified in
         place).  ``nslice=(n0, n1)``: run on that sample range of the saved activations.  ``input_grads``:
         InputLayers whose gradient is wanted.  Returns {InputLayer: DevTensor grad}.
@@ -991,551 +1044,606 @@ class NetPlan:
         ``resume={node: gradient w.r.t. node.out}`` (instead of ``seed``): start from gradients an EARLIER emit of this plan
         left behind (``grads_of``) and walk on from those nodes only -- the tail of a pass whose head another pass already
         ran (step.py: the generator gradient of a per-sample-scalar discriminator)."""
-        ops, st, dev = self.ops, self.store, self.dev
-        n0, n1 = nslice if nslice is not None else (0, self.batch)
-        nb = n1 - n0
-        if transposed is None:
-            transposed = set()      # weights already transposed earlier in this step's program
-
-        def sl(t):
-            return t if nslice is None else t.samples(n0, n1)
-
-        want_in = {id(self.node_of_layer[id(l)]) for l in input_grads}
-        # which nodes need a gradient at all
-        req = {}
-        for n in self.order:
-            has_p = wgrad and n.op in ('conv', 'convpool', 'deconv', 'dense', 'bn', 'upconv')
-            req[id(n)] = has_p or any(req[id(i)] for i in n.inputs) or id(n) in want_in
-        grads, written = {}, set()
-        expands, expand_params, frames = [], [], []
-        key = (tag, n0, n1)
-        cache = self._scratch.setdefault(key, {})
-        for n in self.order:                # flags of an earlier emit of the same (tag, slice): every emit decides afresh
-            n.aux.pop(('grad_is_pre', key), None)
-
-        def grad_of(n):
-            """gradient buffer w.r.t. n.out (allocated once per (tag, slice))."""
-            if id(n) in grads:
-                return grads[id(n)]
-            if id(n) in cache:
-                g = cache[id(n)]
-            elif n.alias is not None:
-                cat, c0 = n.alias
-                g = grad_of(cat).channels(c0, c0 + n.shape[1])
-            else:
-                g = dev.empty((nb * (n.shape[0] // self.batch),) + tuple(n.shape[1:]))
-            cache[id(n)] = g
-            grads[id(n)] = g
-            return g
-
-        def mark_written(n):
-            written.add(id(n))
-            if n.op == 'concat':
-                for i in n.inputs:
-                    if i.alias is not None and i.alias[0] is n:
-                        if id(i) in written:
-                            raise NotImplementedError("gradient of a concat input written before the concat's own "
-                                                      "consumer ran (unsupported graph ordering)")
-                        mark_written(i)
-
-        def target(n):
-            """-> (grad tensor of n, accumulate flag) for a consumer about to write it."""
-            if n.alias is not None and id(n) not in written:
-                # a concat input's gradient slice is first written by the concat's own consumer
-                raise NotImplementedError("gradient of a ConcatLayer input written before the concat's consumer "
-                                          "ran (unsupported graph ordering)")
-            return grad_of(n), id(n) in written
-
+        bp = _BackwardPass(self, prog, nslice, wgrad, input_grads, tag, transposed, on_grads)
         if resume is None:
-            grads[id(self.out_node)] = seed
-            written.add(id(self.out_node))
-            mark_written(self.out_node)
+            bp.start(self.out_node, seed)
         else:
             for rn, rg in resume.items():
-                grads[id(rn)] = rg
-                written.add(id(rn))
-                mark_written(rn)
-                # what the earlier pass left in the buffer of a layer with its own nonlinearity is the gradient in FRONT of it
-                # (act_bwd runs in place, or the consumer's data gradient applied it in its epilogue)
-                if rn.op in ('conv', 'deconv', 'dense') and rn.act != linear:
-                    rn.aux[('grad_is_pre', key)] = True
-
-        def done(*params):
-            if on_grads is not None and wgrad:
-                on_grads(prog, [p for p in params if p is not None])
-
-        hi_grads = set()        # BatchNorm nodes whose output gradient is held in the interleaved layout of their pp_to_hi reader
-        gq_ready = set()        # nodes whose output-gradient q tensor was written by the kernel that produced the gradient
-        pooled_c = {}           # convpool nodes whose gradient also exists in the sparse instruction's operand form
-
-        def gradq_of(n, G, pack=True):
-            """q copy of the (final) output gradient G of node n: the operand of its low-precision data / weight
-            gradient.  Written by G's producer where that kernel has a q epilogue, else packed here in one pass."""
-            if not self.use_q or G.Cc % 8:
-                return None
-            Gq = cache.get(('gq', id(n)))
-            if Gq is None:
-                Gq = cache[('gq', id(n))] = QTensor.empty(dev, G.shape, self.dtype)
-            if pack and id(n) not in gq_ready:
-                gq_ready.add(id(n))
-                prog.append(("q_pack", lambda G=G, Gq=Gq: ops.q_pack(G, Gq), pack_meta(G)))
-            return Gq
-
-        def fused_gq(xin, gi, acc):
-            """may the data-gradient kernel that writes gi (the gradient of xin's output) also write its q copy?  Only
-            when gi is final as written: single consumer, nothing accumulates into it, no activation backward runs on
-            it afterwards, and xin's own backward is a low-precision product that reads it."""
-            if not self.use_q or acc or xin.op != 'conv' or len(xin.consumers) != 1 or gi.Cc % 8:
-                return None
-            if xin.act != linear and not xin.aux.get(('grad_is_pre', key)):
-                return None
-            dq = self._desc(xin, sl(xin.inputs[0].out), gi)
-            if not (self._lp(dq, 1) or self._lp(dq, 2)):
-                return None
-            gq_ready.add(id(xin))
-            return gradq_of(xin, gi, pack=False)
-
+                bp.start(rn, rg, resumed=True)
         for n in reversed(self.order):
-            if id(n) not in written or not req[id(n)]:
-                continue
-            G = grad_of(n)
-            if n.op in ('input', 'concat'):
-                if n.op == 'concat':
-                    c0 = 0
-                    for i in n.inputs:
-                        if (i.alias is None or i.alias[0] is not n) and req[id(i)]:
-                            gi, acc = target(i)
-                            src = G.channels(c0, c0 + i.shape[1])
-                            prog.append(("concat_bwd_copy", lambda a=src, b=gi, acc=acc: ops.copy_view(a, b, acc)))
-                            mark_written(i)
-                        c0 += i.shape[1]
-                continue
-            xin = n.inputs[0]
-            x, y = sl(xin.out), sl(n.out)
-            if n.op == 'convpool' and n.act.kind in ('linear', 'relu', 'lrelu') and os.environ.get("GHM_POOL_READ_Y") is None:
-                y = None                    # the mask carries the sign of the pooled activation: its backward never reads it
-            a = n.act
-            need_dx = req[id(xin)]
-            if n.op == 'convpool':
-                fs = n.aux['full_shape']
-                per = int(np.prod(n.shape[1:]))                  # mask bytes per sample
-                # the discriminator's first block (one input channel): both gradients straight from the pooled operands
-                # (csrc/conv_pool_bwd.hip) -- the 537 MB full-resolution gradient is neither written nor read
-                dS = self._desc(n, x, self._full(n, nb))
-                sparse = int(ops.pool_bwd_sparse_supported(dS, a.kind) or 0)
-                if (sparse & 1 or not wgrad) and (sparse & 2 or not need_dx) and sparse:
-                    l = n.layer
-                    mptr = n.aux['mask'] + n0 * per
-                    if wgrad:
-                        self._grow_wgrad_ws(ops.pool_wgrad_sparse_workspace(dS))
-                        gw, gb = st.grad(l.W), st.grad(l.b)
-                        wo, wdev = ops, None
-                        if self.side is not None:
-                            wdev, wo = self.side
-                            prog.append(("fork", lambda wdev=wdev: wdev.wait_for(dev), None, wdev))
-                        prog.append(("conv_wgrad", lambda dS=dS, x=x, m=mptr, y=y, G=G, gw=gw, gb=gb, a=a, aw=accumulate_wgrad, wo=wo:
-                                     wo.conv2d_pool_wgrad_sparse(dS, x, m, y, G, gw, gb, self.wgrad_ws, a.kind, a.alpha, aw),
-                                     pool_sparse_meta(dS, 2), wdev))
-                        done(l.W, l.b)
-                    if need_dx:
-                        gi, acc = target(xin)
-                        w = st.value(l.W)
-                        dG = self._desc(n, gi, self._full(n, nb))        # the kernel strides dx by ITS sample stride, not x's
-                        prog.append(("conv_dgrad", lambda dG=dG, m=mptr, y=y, G=G, w=w, gi=gi, a=a, acc=acc:
-                                     ops.conv2d_pool_dgrad_sparse(dG, m, y, G, w, gi, a.kind, a.alpha, acc), pool_sparse_meta(dG, 1)))
-                        mark_written(xin)
-                    continue
-                # otherwise: the gradient of the conv's (never materialised in the forward pass) full-resolution output from
-                # the arg-max mask, the pooled value (sign -> activation derivative) and the pooled gradient; then an
-                # ordinary conv backward
-                Gf = cache.get(('full', id(n)))
-                if Gf is None:
-                    Gf = cache[('full', id(n))] = dev.empty((nb,) + tuple(fs[1:]))
-                mptr = n.aux['mask'] + n0 * per
-                # with the weight gradients wanted, the same pass also sums what it writes per channel: the bias gradient
-                gb_fused = st.grad(n.layer.b) if wgrad else None
-                # who reads the full-resolution gradient: the conv's low-precision data / weight gradients read its q copy;
-                # the fp32 tensor is written only if a fp32 kernel reads it (thin first layer, geometries not served)
-                dF = self._desc(n, x, Gf)
-                xq_ = xin.outq if nslice is None else (xin.outq.samples(n0, n1) if xin.outq is not None else None)
-                w_q = xq_ is not None and self._wq(dF)
-                d_lp = self.use_q and need_dx and self._lp(self._desc(n, sl(xin.out), Gf), 1)
-                q_wanted = (wgrad and w_q) or d_lp
-                Gfq = gradq_of(n, Gf, pack=False) if (q_wanted and self.q_epi and Gf.Cc % 8 == 0 and Gf.H % 2 == 0
-                                                      and Gf.W % 4 == 0) else None
-                if Gfq is not None:         # the full-resolution gradient (if anybody reads it) and its q copy in one pass
-                    gq_ready.add(id(n))
-                    Gf32 = None if ((w_q or not wgrad) and (d_lp or not need_dx)) else Gf
-                    prog.append(("maxpool_mask_bwd", lambda m=mptr, y=y, G=G, Gf32=Gf32, Gfq=Gfq, a=a, gb=gb_fused, aw=accumulate_wgrad:
-                                 ops.maxpool2_mask_bwd_q(m, y, G, Gf32, Gfq, a.kind, a.alpha, gb, aw)))
-                    # the same gradient once more as half-width rows + column bits: the operand of the sparse matrix
-                    # instruction, for the 5x5 weight gradient (DESIGN 4g; rows with a tied window row stay on the dense q copy)
-                    if wgrad and w_q and ops.wgrad_pooled_split_supported(dF, self.dtype):
-                        pc = cache.get(('pooled_c', id(n), nb))
-                        if pc is None:
-                            Kp, Hf, Wf = Gf.Cc, Gf.H, Gf.W
-                            pc = cache[('pooled_c', id(n), nb)] = (
-                                QTensor.empty(dev, (nb, Kp, Hf, Wf // 2), self.dtype),
-                                dev.alloc(nb * (Kp // 8) * Hf * (Wf // 32) * 16 + 256), dev.alloc(nb * Hf * 4 + 256))
-                        # (written by the stream that runs the weight gradient, its only reader: see conv_wgrad below)
-                        pooled_c[id(n)] = pc + (mptr, y, G, a)
-                else:
-                    prog.append(("maxpool_mask_bwd", lambda m=mptr, y=y, G=G, Gf=Gf, a=a, gb=gb_fused, aw=accumulate_wgrad:
-                                 ops.maxpool2_mask_bwd(m, y, G, Gf, a.kind, a.alpha, gb, aw)))
-                G, a = Gf, linear
-            if n.op in ('conv', 'convpool', 'deconv', 'dense'):
-                if a != linear and not n.aux.get(('grad_is_pre', key)):
-                    prog.append(("act_bwd", lambda G=G, y=y, a=a: ops.act_bwd(G, y, G, a.kind, a.alpha)))
-                l = n.layer
-                w = st.value(l.W)
-                if n.op == 'deconv':
-                    d = self._desc(n, G, x)          # conv input side = deconv output grad, output side = x
-                else:
-                    d = self._desc(n, x, G)
-                # the q copy of the output gradient, for the low-precision weight gradient (before its stream forks off)
-                xq = None if (nslice is not None and xin.outq is None) else (xin.outq if nslice is None else
-                                                                             (xin.outq.samples(n0, n1) if xin.outq is not None else None))
-                wq_form = wgrad and n.op in ('conv', 'convpool') and xq is not None and self._wq(d)
-                Gq_w = gradq_of(n, G) if wq_form else None
-                if wgrad:
-                    self._need_wgrad_ws(d)
-                    gw, gb = st.grad(l.W), st.grad(l.b)
-                    aw = accumulate_wgrad
-                    wo, wdev = ops, None
-                    if self.side is not None:
-                        wdev, wo = self.side
-                        prog.append(("fork", lambda wdev=wdev: wdev.wait_for(dev), None, wdev))
-                    if Gq_w is not None and id(n) in pooled_c:
-                        pc = pooled_c[id(n)]
-                        prog.append(("maxpool_mask_compress", lambda pc=pc, wo=wo:
-                                     wo.maxpool2_mask_bwd_compress_q(pc[3], pc[4], pc[5], pc[0], pc[1], pc[2], pc[6].kind, pc[6].alpha),
-                                     None, wdev))
-                        prog.append(("conv_wgrad", lambda d=d, xq=xq, Gq=Gq_w, pc=pc, gw=gw, aw=aw, wo=wo:
-                                     wo.conv2d_wgrad_pooled_split(d, xq, Gq, pc[0], pc[1], pc[2], gw, self.wgrad_ws, self.dtype, aw),
-                                     sparse_meta(conv_meta(ops, d, 2, self.dtype)), wdev))
-                    elif Gq_w is not None:
-                        prog.append(("conv_wgrad", lambda d=d, xq=xq, Gq=Gq_w, gw=gw, aw=aw, wo=wo:
-                                     wo.conv2d_wgrad_lp_q(d, xq, Gq, gw, self.wgrad_ws, self.dtype, aw),
-                                     conv_meta(ops, d, 2, self.dtype), wdev))
-                    elif n.op == 'deconv':
-                        prog.append(("deconv_wgrad", lambda d=d, G=G, x=x, gw=gw, aw=aw, wo=wo:
-                                     wo.conv2d_wgrad(d, G, x, gw, self.wgrad_ws, aw), conv_meta(ops, d, 2), wdev))
-                    elif n.op in ('conv', 'convpool') and self._lp(d, 2):
-                        prog.append(("conv_wgrad", lambda d=d, G=G, x=x, gw=gw, aw=aw, wo=wo:
-                                     wo.conv2d_wgrad_lp(d, x, G, gw, self.wgrad_ws, self.dtype, aw),
-                                     conv_meta(ops, d, 2, self.dtype), wdev))
-                    else:
-                        prog.append(("%s_wgrad" % ('conv' if n.op == 'convpool' else n.op), lambda d=d, G=G, x=x, gw=gw, aw=aw, wo=wo:
-                                     wo.conv2d_wgrad(d, x, G, gw, self.wgrad_ws, aw), conv_meta(ops, d, 2), wdev))
-                    # a bias that feeds a BatchNorm has an identically zero gradient (the BN backward output sums to
-                    # zero per channel): its slice of the zero-initialised gradient buffer is simply never written
-                    bn_fed = len(n.consumers) == 1 and n.consumers[0].op == 'bn' and n.act == linear
-                    if not bn_fed and n.op != 'convpool':       # convpool: summed by the mask backward pass above
-                        prog.append(("bias_grad", lambda G=G, gb=gb, aw=aw, wo=wo: wo.channel_sum(G, gb, aw), None, wdev))
-                    done(l.W, l.b)
-                if need_dx:
-                    gi, acc = target(xin)
-                    # the producer's own nonlinearity (a conv -> LeakyRectify -> conv chain without BatchNorm: the
-                    # PatchGAN, p2p.py:285-286) differentiated in THIS data gradient's epilogue instead of a separate
-                    # read-modify-write pass over the gradient tensor
-                    form = 0
-                    if (not acc and n.op in ('conv', 'convpool') and xin.op in ('conv', 'deconv', 'dense')
-                            and xin.act.kind in ('relu', 'lrelu') and len(xin.consumers) == 1 and not xin.aux.get(('grad_is_pre', key))):
-                        form = ops.dgrad_dact_supported(self._desc(n, gi, G), self.dtype) or 0
-                    if form:
-                        d2 = self._desc(n, gi, G)
-                        dt = 'f32'
-                        if form == 1:
-                            wsel = w
-                        elif form == 2:
-                            wsel = st.transposed(l.W)
-                            if id(l.W) not in transposed:
-                                transposed.add(id(l.W))
-                                prog.append(("transpose_w", lambda d=d2, w=w, wT=wsel: ops.transpose_weights(d, w, wT)))
-                        else:
-                            wsel, dt = self._lp_pack_entry(prog, d2, w, ('w', id(l.W)), True, transposed), self.dtype
-                        xa = xin.act
-                        xin.aux[('grad_is_pre', key)] = True
-                        Gq = gradq_of(n, G) if form == 3 else None
-                        if Gq is not None and (ops.lp_q_direct(d2, 1, self.dtype) or self.dtype in SPLITS):
-                            giq = fused_gq(xin, gi, acc) if ops.lp_q_direct(d2, 1, self.dtype) else None
-                            # split modes: the slope from the sign of the producer's q copy (2 bytes per element, and the
-                            # producer's fp32 activation need not exist: _act_fp32_dropped)
-                            ysrc = x
-                            if self.dtype in SPLITS and xin.outq is not None and gi.Cc % 8 == 0 and not os.environ.get("GHM_DACT_FP32"):
-                                ysrc = xin.outq if nslice is None else xin.outq.samples(n0, n1)
-                            prog.append(("conv_dgrad", lambda d=d2, Gq=Gq, wsel=wsel, gi=gi, giq=giq, x=ysrc, xa=xa:
-                                         ops.conv2d_dgrad_dact_lp_q(d, Gq, wsel, gi, giq, x, xa.kind, xa.alpha, self.dtype),
-                                         conv_meta(ops, d2, 3, dt, extra=" +dact" + (" +q" if giq is not None else ""))))
-                        else:
-                            prog.append(("conv_dgrad", lambda d=d2, G=G, wsel=wsel, gi=gi, x=x, xa=xa, dt=dt:
-                                         ops.conv2d_dgrad_dact(d, G, wsel, gi, x, xa.kind, xa.alpha, dt),
-                                         conv_meta(ops, d2, 3 if form != 1 else 1, dt)))
-                    elif n.op == 'deconv':
-                        d2 = self._desc(n, G, gi)
-                        prog.append(("deconv_dgrad", lambda d=d2, G=G, w=w, gi=gi, acc=acc:
-                                     ops.conv2d_fwd(d, G, w, None, gi, 'linear', 0.0, acc), conv_meta(ops, d2, 0)))
-                    elif n.op in ('conv', 'convpool') and self._lp(self._desc(n, gi, G), 1):
-                        d2 = self._desc(n, gi, G)
-                        wqT = self._lp_pack_entry(prog, d2, w, ('w', id(l.W)), True, transposed)
-                        Gq = gradq_of(n, G)
-                        if Gq is not None:
-                            giq = fused_gq(xin, gi, acc) if ops.lp_q_direct(d2, 1, self.dtype) else None
-                            if giq is None:
-                                gq_ready.discard(id(xin))
-                            prog.append(("conv_dgrad", lambda d=d2, Gq=Gq, wqT=wqT, gi=gi, giq=giq, acc=acc:
-                                         ops.conv2d_dgrad_lp_q(d, Gq, wqT, gi, giq, self.dtype, None, 'linear', 0.0, acc),
-                                         conv_meta(ops, d2, 3, self.dtype,
-                                                   extra=(" +q" if giq is not None else "") + (" +acc" if acc else ""))))
-                        else:
-                            prog.append(("conv_dgrad", lambda d=d2, G=G, wqT=wqT, gi=gi, acc=acc:
-                                         ops.conv2d_dgrad_lp(d, G, wqT, gi, self.dtype, None, 'linear', 0.0, acc),
-                                         conv_meta(ops, d2, 3, self.dtype)))
-                    elif n.op in ('conv', 'convpool') and self._use_dgrad_t(self._desc(n, gi, G), l.W):
-                        # data gradient as a forward-form conv on the transposed weights (LDS-patch kernels)
-                        d2 = self._desc(n, gi, G)
-                        wT = st.transposed(l.W)
-                        if id(l.W) not in transposed:
-                            transposed.add(id(l.W))
-                            prog.append(("transpose_w", lambda d=d2, w=w, wT=wT: ops.transpose_weights(d, w, wT)))
-                        prog.append(("conv_dgrad", lambda d=d2, G=G, wT=wT, gi=gi, acc=acc:
-                                     ops.conv2d_dgrad_t(d, G, wT, gi, None, 'linear', 0.0, acc), conv_meta(ops, d2, 3)))
-                    else:
-                        d2 = self._desc(n, gi, G)
-                        prog.append(("%s_dgrad" % ('conv' if n.op == 'convpool' else n.op), lambda d=d2, G=G, w=w, gi=gi, acc=acc:
-                                     ops.conv2d_dgrad(d, G, w, gi, None, 'linear', 0.0, acc), conv_meta(ops, d2, 1)))
-                    mark_written(xin)
-            elif n.op == 'upconv':
-                if nslice is not None:
-                    raise NotImplementedError("sample slices through a collapsed up-sample convolution")
-                if a != linear:
-                    prog.append(("act_bwd", lambda G=G, y=y, a=a: ops.act_bwd(G, y, G, a.kind, a.alpha)))
-                l = n.layer
-                d = self._upconv_desc(n, x)
-                C, K = x.Cc, n.shape[1]
-                G4 = G.reshape((x.N, 4 * K, x.H, x.W))
-                wpc, wpcT, dwpc = n.aux['wpc'], n.aux['wpcT'], n.aux['dwpc']
-                xq = xin.outq
-                G4q_w = gradq_of(n, G4) if (wgrad and xq is not None and self._wq(d)) else None
-                bl = n.attrs.get('mode') == 1
-                ulab = 'blconv' if bl else 'upconv'
-                if bl:      # the six border lines of the fine gradient, for both frame gradients (before the gradient stream forks)
-                    prog.append(("blconv_frame_gather", lambda G4=G4, C=C, K=K, dyl=n.aux['dyl']: ops.blconv_frame_gather(G4, C, K, dyl)))
-                if wgrad:
-                    self._need_wgrad_ws(d)
-                    gw, gb = st.grad(l.W), st.grad(l.b)
-                    aw = accumulate_wgrad
-                    wo, wdev = ops, None
-                    if self.side is not None:
-                        wdev, wo = self.side
-                        prog.append(("fork", lambda wdev=wdev: wdev.wait_for(dev), None, wdev))
-                    if G4q_w is not None and self._bl_skip(n, d, 2):
-                        prog.append((ulab + "_wgrad", lambda d=d, xq=xq, G4q=G4q_w, dwpc=dwpc, wo=wo:
-                                     wo.blconv_wgrad_split(d, xq, G4q, dwpc, self.wgrad_ws, self.dtype, False),
-                                     bl_meta(conv_meta(ops, d, 2, self.dtype)), wdev))
-                    elif G4q_w is not None:
-                        prog.append((ulab + "_wgrad", lambda d=d, xq=xq, G4q=G4q_w, dwpc=dwpc, wo=wo:
-                                     wo.conv2d_wgrad_lp_q(d, xq, G4q, dwpc, self.wgrad_ws, self.dtype, False),
-                                     conv_meta(ops, d, 2, self.dtype), wdev))
-                    elif self._lp(d, 2):
-                        prog.append((ulab + "_wgrad", lambda d=d, x=x, G4=G4, dwpc=dwpc, wo=wo:
-                                     wo.conv2d_wgrad_lp(d, x, G4, dwpc, self.wgrad_ws, self.dtype, False),
-                                     conv_meta(ops, d, 2, self.dtype), wdev))
-                    else:
-                        prog.append((ulab + "_wgrad", lambda d=d, x=x, G4=G4, dwpc=dwpc, wo=wo:
-                                     wo.conv2d_wgrad(d, x, G4, dwpc, self.wgrad_ws, False), conv_meta(ops, d, 2), wdev))
-                    expands.append((dwpc, gw, C, K, n.attrs.get('mode', 0)))      # 3x3 -> 5x5 (-> fine 3x3) gradient expansion: one launch for all layers, below
-                    if bl:
-                        frames.append((n.aux['dyl'], n.aux['fl'], gw, x.N, C, K, x.H, x.W))
-                    bn_fed = len(n.consumers) == 1 and n.consumers[0].op == 'bn' and n.act == linear
-                    if not bn_fed:
-                        prog.append(("bias_grad", lambda G=G, gb=gb, aw=aw, wo=wo: wo.channel_sum(G, gb, aw), None, wdev))
-                    done(l.b)                              # l.W: written by the batched 3x3 -> 5x5 expansion below
-                    expand_params.append(l.W)
-                if need_dx:
-                    gi, acc = target(xin)
-                    if self._lp(d, 1):
-                        wqT = self._lp_pack_entry(prog, d, wpc, ('c', id(l.W)), True, transposed)
-                        G4q = gradq_of(n, G4)
-                        if G4q is not None and self._bl_skip(n, d, 1):
-                            prog.append((ulab + "_dgrad", lambda d=d, G4q=G4q, wqT=wqT, gi=gi, acc=acc:
-                                         ops.blconv_dgrad_split(d, G4q, wqT, gi, self.dtype, acc),
-                                         bl_meta(conv_meta(ops, d, 3, self.dtype))))
-                        elif G4q is not None:
-                            prog.append((ulab + "_dgrad", lambda d=d, G4q=G4q, wqT=wqT, gi=gi, acc=acc:
-                                         ops.conv2d_dgrad_lp_q(d, G4q, wqT, gi, None, self.dtype, None, 'linear', 0.0, acc),
-                                         conv_meta(ops, d, 3, self.dtype)))
-                        else:
-                            prog.append((ulab + "_dgrad", lambda d=d, G4=G4, wqT=wqT, gi=gi, acc=acc:
-                                         ops.conv2d_dgrad_lp(d, G4, wqT, gi, self.dtype, None, 'linear', 0.0, acc),
-                                         conv_meta(ops, d, 3, self.dtype)))
-                    elif C > 4 and ops.dgrad_t_supported(d):
-                        if ('c', id(l.W)) not in transposed:
-                            transposed.add(('c', id(l.W)))
-                            prog.append(("transpose_w", lambda d=d, wpc=wpc, wpcT=wpcT: ops.transpose_weights(d, wpc, wpcT)))
-                        prog.append((ulab + "_dgrad", lambda d=d, G4=G4, wpcT=wpcT, gi=gi, acc=acc:
-                                     ops.conv2d_dgrad_t(d, G4, wpcT, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, 3)))
-                    else:
-                        prog.append((ulab + "_dgrad", lambda d=d, G4=G4, wpc=wpc, gi=gi, acc=acc:
-                                     ops.conv2d_dgrad(d, G4, wpc, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, 1)))
-                    if bl:
-                        prog.append(("blconv_frame_dgrad", lambda dyl=n.aux['dyl'], w3=st.value(l.W), gi=gi, K=K:
-                                     ops.blconv_frame_dgrad(dyl, w3, gi, K)))
-                    mark_written(xin)
-            elif n.op == 'dropout':
-                if need_dx:
-                    gi, acc = target(xin)
-                    if acc or nslice is not None:
-                        raise NotImplementedError("DropoutLayer input with several consumers / sample slices")
-                    # same key, same counter value as the forward pass of this step -> the same mask
-                    prog.append(("dropout_bwd", lambda G=G, gi=gi, p=n.attrs['p'], k=n.aux['key'], c=self.rng_counter:
-                                 ops.dropout(G, gi, p, k, c)))
-                    mark_written(xin)
-            elif n.op == 'pp_to_hi':
-                if need_dx and nslice is None and self._bn_hi(xin) and G.nstride % 2 == 0:
-                    # the BatchNorm backward reads this gradient through the inverse permutation: no hi_to_pp pass
-                    grads[id(xin)] = G
-                    hi_grads.add(id(xin))
-                    mark_written(xin)
-                elif need_dx:
-                    gi, acc = target(xin)
-                    if acc or nslice is not None:
-                        raise NotImplementedError("parity-planar tensor with several consumers / sample slices")
-                    prog.append(("hi_to_pp", lambda G=G, gi=gi: ops.hi_to_pp(G, gi)))
-                    mark_written(xin)
-            elif n.op == 'bn':
-                l = n.layer
-                # (the backward kernels recompute y = act(bn(x)) from x instead of reading the output tensor: bit-identical
-                # to the forward value, one tensor less to read in both of their passes)
-                gam, bet = st.value(l.gamma), st.value(l.beta)
-                if wgrad:
-                    dg, db, aw = st.grad(l.gamma), st.grad(l.beta), accumulate_wgrad
-                else:
-                    C = n.shape[1]
-                    dg, db, aw = self._bn_scratch.channels(0, C), self._bn_scratch.channels(C, 2 * C), False
-                gi, acc = target(xin)
-                dst = gi
-                if acc:
-                    dst = dev.empty(gi.shape) if ('bn_tmp', id(n)) not in cache else cache[('bn_tmp', id(n))]
-                    cache[('bn_tmp', id(n))] = dst
-                # the convolution in front of this BatchNorm reads gi as the operand of its low-precision data / weight
-                # gradients: the apply pass writes the q copy itself -- and no fp32 gradient at all when both read q
-                giq, gi32 = None, True
-                inst = getattr(n, 'instance', False)
-                if (self.q_epi and not acc and nslice is None and self.bn_groups == 1 and not inst and xin.op in ('conv', 'upconv')
-                        and len(xin.consumers) == 1 and xin.act == linear and gi.HW % 2 == 0 and gi.Cc % 8 == 0
-                        and gi.nstride % 2 == 0):
-                    xx = xin.inputs[0]
-                    if xin.op == 'conv':
-                        dq, gview = self._desc(xin, xx.out, gi), gi
-                    else:
-                        dq = self._upconv_desc(xin, xx.out)
-                        gview = gi.reshape((xx.out.N, 4 * xin.shape[1], xx.out.H, xx.out.W))
-                    w_q = xx.outq is not None and self._wq(dq)
-                    d_q = self._lp(dq, 1) or not req[id(xx)]
-                    if (w_q or not wgrad) and (self._lp(dq, 1) or w_q):
-                        giq = gradq_of(xin, gview, pack=False).reshape(gi.shape)
-                        gq_ready.add(id(xin))
-                        gi32 = not ((w_q or not wgrad) and d_q) or xin.attrs.get('mode') == 1     # (the frame reads its border lines)
-                if inst:
-                    if nslice is not None:
-                        raise NotImplementedError("InstanceNorm backward on a sample slice")
-                    prog.append(("in_bwd", lambda G=G, x=x, dst=dst, m=n.aux['mean'], iv=n.aux['inv'], gam=gam, bet=bet, dg=dg, db=db,
-                                 a=a, aw=aw, grp=n.aux['group']:
-                                 ops.instance_norm_bwd(G, x, dst, m, iv, gam, bet, dg, db, self.bn_ws, a.kind, a.alpha, aw, grp)))
-                elif id(n) in hi_grads:
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    dst32 = dst if (giq is None or gi32) else None
-                    prog.append(("bn_bwd", lambda G=G, x=x, dst32=dst32, giq=giq, m=m, iv=iv, gam=gam, bet=bet, dg=dg, db=db, a=a, aw=aw:
-                                 ops.bn_backward_hi(G, x, dst32, giq, m, iv, gam, bet, dg, db, self.bn_ws, a.kind, a.alpha, aw)))
-                elif giq is not None:
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    dst32 = dst if gi32 else None
-                    prog.append(("bn_bwd", lambda G=G, x=x, dst32=dst32, giq=giq, m=m, iv=iv, gam=gam, bet=bet, dg=dg, db=db, a=a, aw=aw:
-                                 ops.bn_backward_q(G, None, x, dst32, m, iv, gam, dg, db, self.bn_ws, giq, a.kind, a.alpha, aw, bet)))
-                elif self.bn_groups == 2:
-                    hb = self.batch // 2
-                    halves = (0, 1) if nslice is None else ((n0 // hb,) if (n1 - n0) == hb and n0 % hb == 0 else None)
-                    if halves is None:
-                        raise NotImplementedError("sample slice that is not one half of a [real | fake] batch")
-                    for idx, h in enumerate(halves):
-                        sub = (lambda t, h=h: t.samples(h * hb, (h + 1) * hb)) if nslice is None else (lambda t: t)
-                        m, iv = n.aux['mean_g'][h], n.aux['inv_g'][h]
-                        awh = aw or idx > 0          # the second half adds to dgamma / dbeta
-                        prog.append(("bn_bwd", lambda G=sub(G), x=sub(x), dst=sub(dst), m=m, iv=iv, gam=gam, bet=bet,
-                                     dg=dg, db=db, a=a, awh=awh:
-                                     ops.bn_backward_x(G, x, dst, m, iv, gam, bet, dg, db, self.bn_ws, a.kind, a.alpha, awh)))
-                else:
-                    m, iv = n.aux['mean'], n.aux['inv']
-                    prog.append(("bn_bwd", lambda G=G, x=x, dst=dst, m=m, iv=iv, gam=gam, bet=bet, dg=dg, db=db, a=a, aw=aw:
-                                 ops.bn_backward_x(G, x, dst, m, iv, gam, bet, dg, db, self.bn_ws, a.kind, a.alpha, aw)))
-                if acc:
-                    prog.append(("bn_bwd_acc", lambda dst=dst, gi=gi: ops.copy_view(dst, gi, True)))
-                done(l.gamma, l.beta)
-                mark_written(xin)
-            elif n.op == 'act':
-                if need_dx:
-                    gi, acc = target(xin)
-                    prog.append(("act_bwd", lambda G=G, y=y, gi=gi, a=a, acc=acc:
-                                 ops.act_bwd(G, y, gi, a.kind, a.alpha, acc)))
-                    mark_written(xin)
-            elif n.op == 'reshape':
-                if need_dx:
-                    if id(xin) in grads or id(xin) in cache or xin.alias is not None:
-                        gi, acc = target(xin)
-                        prog.append(("reshape_bwd", lambda G=G, gi=gi, acc=acc:
-                                     ops.copy_view(G.reshape(gi.shape), gi, acc)))
-                    else:
-                        grads[id(xin)] = cache[id(xin)] = G.reshape((nb,) + tuple(xin.shape[1:]))
-                    mark_written(xin)
-            elif n.op in ('up_nearest', 'up_bilinear'):
-                if need_dx:
-                    gi, acc = target(xin)
-                    fn = ops.upsample_nearest2_bwd if n.op == 'up_nearest' else ops.upsample_bilinear2_bwd
-                    prog.append(("%s_bwd" % n.op, lambda G=G, gi=gi, acc=acc, fn=fn: fn(G, gi, acc)))
-                    mark_written(xin)
-            elif n.op == 'maxpool':
-                if need_dx:
-                    gi, acc = target(xin)
-                    if acc:
-                        raise NotImplementedError("maxpool input with several consumers")
-                    fa = linear
-                    if xin.op in ('conv', 'deconv', 'dense') and len(xin.consumers) == 1 and xin.act.kind in ('lrelu', 'relu'):
-                        # fold the producer's LeakyReLU/ReLU backward into the pooling scatter (mask from the output sign)
-                        fa = xin.act
-                        xin.aux[('grad_is_pre', key)] = True
-                    prog.append(("maxpool_bwd", lambda x=x, y=y, G=G, gi=gi, fa=fa:
-                                 ops.maxpool2_bwd(x, y, G, gi, fa.kind, fa.alpha)))
-                    mark_written(xin)
-            elif n.op == 'avgpool':
-                if need_dx:
-                    gi, acc = target(xin)
-                    if acc:
-                        raise NotImplementedError("avgpool input with several consumers")
-                    prog.append(("avgpool_bwd", lambda G=G, gi=gi, p=n.attrs['p']: ops.avgpool_bwd(G, gi, p)))
-                    mark_written(xin)
-            else:
-                raise NotImplementedError(n.op)
-        if expands:
-            # after the last collapsed layer's weight gradient, on the lane the weight gradients run on
-            wo, wdev = (self.side[1], self.side[0]) if self.side is not None else (ops, None)
-            tkey = ('expand', tuple(int(e[0].ptr) for e in expands))
-            tab = self._scratch.setdefault('tables', {}).get(tkey)
-            if tab is None:
-                tab = self._scratch['tables'][tkey] = wo.expand_table(expands)
-            prog.append(("expand_wgrad", lambda tab=tab, aw=accumulate_wgrad, wo=wo: wo.upconv_expand_batched(tab, aw),
-                         None, wdev))
-            for dyl, fl, gw, N_, C_, K_, h_, w_ in frames:       # the frame's share of the fine weight gradients, on top
-                prog.append(("blconv_frame_wgrad", lambda dyl=dyl, fl=fl, gw=gw, N_=N_, C_=C_, K_=K_, h_=h_, w_=w_, wo=wo:
-                             wo.blconv_frame_wgrad(dyl, fl, gw, N_, C_, K_, h_, w_), None, wdev))
-            done(*expand_params)
-        self._last_grads = dict(grads)
-        return {l: (grad_of(self.node_of_layer[id(l)]) if id(self.node_of_layer[id(l)]) in written else None)
+            bp.lower(n)
+        bp.finish()
+        self._last_grads = dict(bp.grads)
+        return {l: (bp.grad_of(self.node_of_layer[id(l)]) if id(self.node_of_layer[id(l)]) in bp.written else None)
                 for l in input_grads}
 
     def grads_of(self, node):
         """the buffer the LAST emit_backward of this plan holds the gradient w.r.t. ``node.out`` in (None: never written)"""
-        return getattr(self, '_last_grads', {}).get(id(node))
+        return self._last_grads.get(id(node))
+
+
+class _BackwardPass:
+    """One NetPlan.emit_backward call: the state the per-op backward lowerings share (which gradients exist, which are
+    written, the scratch cache of this (tag, slice)) and one method per op (bwd_<op>).  Every method appends to
+    ``prog`` in the order the launches run; buffers are allocated where they are first needed (the order is behaviour)."""
+
+    def __init__(self, plan, prog, nslice, wgrad, input_grads, tag, transposed, on_grads):
+        self.plan, self.prog, self.nslice, self.wgrad, self.on_grads = plan, prog, nslice, wgrad, on_grads
+        self.ops, self.st, self.dev, self.dtype = plan.ops, plan.store, plan.dev, plan.dtype
+        self.n0, self.n1 = nslice if nslice is not None else (0, plan.batch)
+        self.nb = self.n1 - self.n0
+        self.transposed = transposed if transposed is not None else set()   # weights already transposed earlier in this step's program
+        want_in = {id(plan.node_of_layer[id(l)]) for l in input_grads}
+        self.req = {}               # which nodes need a gradient at all
+        for n in plan.order:
+            has_p = wgrad and n.op in ('conv', 'convpool', 'deconv', 'dense', 'bn', 'upconv')
+            self.req[id(n)] = has_p or any(self.req[id(i)] for i in n.inputs) or id(n) in want_in
+        self.grads, self.written = {}, set()
+        self.expands, self.expand_params, self.frames = [], [], []
+        self.key = (tag, self.n0, self.n1)
+        self.cache = plan._scratch.setdefault(self.key, {})
+        for n in plan.order:        # flags of an earlier emit of the same (tag, slice): every emit decides afresh
+            n.aux.pop(('grad_is_pre', self.key), None)
+        self.hi_grads = set()       # BatchNorm nodes whose output gradient is held in the interleaved layout of their pp_to_hi reader
+        self.gq_ready = set()       # nodes whose output-gradient q tensor was written by the kernel that produced the gradient
+        self.pooled_c = {}          # convpool nodes whose gradient also exists in the sparse instruction's operand form
+
+    # ---- state ---------------------------------------------------------------------------------------
+    def sl(self, t):
+        return t if self.nslice is None else t.samples(self.n0, self.n1)
+
+    def slq(self, q):
+        """the pass's sample range of a q tensor (None stays None)"""
+        return q if (q is None or self.nslice is None) else q.samples(self.n0, self.n1)
+
+    def is_pre(self, n):
+        """is what n's gradient buffer holds already the gradient in FRONT of n's own nonlinearity?"""
+        return n.aux.get(('grad_is_pre', self.key))
+
+    def grad_of(self, n):
+        """gradient buffer w.r.t. n.out (allocated once per (tag, slice))."""
+        if id(n) in self.grads:
+            return self.grads[id(n)]
+        if id(n) in self.cache:
+            g = self.cache[id(n)]
+        elif n.alias is not None:
+            cat, c0 = n.alias
+            g = self.grad_of(cat).channels(c0, c0 + n.shape[1])
+        else:
+            g = self.dev.empty((self.nb * (n.shape[0] // self.plan.batch),) + tuple(n.shape[1:]))
+        self.cache[id(n)] = g
+        self.grads[id(n)] = g
+        return g
+
+    def mark_written(self, n):
+        self.written.add(id(n))
+        if n.op == 'concat':
+            for i in n.inputs:
+                if i.alias is not None and i.alias[0] is n:
+                    if id(i) in self.written:
+                        raise NotImplementedError("gradient of a concat input written before the concat's own "
+                                                  "consumer ran (unsupported graph ordering)")
+                    self.mark_written(i)
+
+    def target(self, n):
+        """-> (grad tensor of n, accumulate flag) for a consumer about to write it."""
+        if n.alias is not None and id(n) not in self.written:
+            # a concat input's gradient slice is first written by the concat's own consumer
+            raise NotImplementedError("gradient of a ConcatLayer input written before the concat's consumer "
+                                      "ran (unsupported graph ordering)")
+        return self.grad_of(n), id(n) in self.written
+
+    def start(self, n, g, resumed=False):
+        """the pass starts at node n, whose output gradient g holds"""
+        self.grads[id(n)] = g
+        self.mark_written(n)
+        # what an earlier pass left in the buffer of a layer with its own nonlinearity is the gradient in FRONT of it
+        # (act_bwd runs in place, or the consumer's data gradient applied it in its epilogue)
+        if resumed and n.op in ('conv', 'deconv', 'dense') and n.act != linear:
+            n.aux[('grad_is_pre', self.key)] = True
+
+    def done(self, *params):
+        if self.on_grads is not None and self.wgrad:
+            self.on_grads(self.prog, [p for p in params if p is not None])
+
+    def gradq_of(self, n, G, pack=True):
+        """q copy of the (final) output gradient G of node n: the operand of its low-precision data / weight
+        gradient.  Written by G's producer where that kernel has a q epilogue, else packed here in one pass."""
+        if not self.plan.use_q or G.Cc % 8:
+            return None
+        Gq = self.cache.get(('gq', id(n)))
+        if Gq is None:
+            Gq = self.cache[('gq', id(n))] = QTensor.empty(self.dev, G.shape, self.dtype)
+        if pack and id(n) not in self.gq_ready:
+            self.gq_ready.add(id(n))
+            self.plan._q_pack(self.prog, G, Gq)
+        return Gq
+
+    def fused_gq(self, xin, gi, acc):
+        """may the data-gradient kernel that writes gi (the gradient of xin's output) also write its q copy?  Only
+        when gi is final as written: single consumer, nothing accumulates into it, no activation backward runs on
+        it afterwards, and xin's own backward is a low-precision product that reads it."""
+        plan = self.plan
+        if not plan.use_q or acc or xin.op != 'conv' or len(xin.consumers) != 1 or gi.Cc % 8:
+            return None
+        if xin.act != linear and not self.is_pre(xin):
+            return None
+        dq = plan._desc(xin, self.sl(xin.inputs[0].out), gi)
+        if not (plan._lp(dq, DGRAD) or plan._lp(dq, WGRAD)):
+            return None
+        self.gq_ready.add(id(xin))
+        return self.gradq_of(xin, gi, pack=False)
+
+    def fork(self):
+        """-> (Ops, device entry) the weight / bias gradients of the layer at hand run on: the plan's gradient stream, forked
+        off the main stream here (where their output gradient is ready), or the main stream itself"""
+        if self.plan.side is None:
+            return self.ops, None
+        wdev, wo = self.plan.side
+        dev = self.dev
+        self.prog.append(("fork", lambda: wdev.wait_for(dev), None, wdev))
+        return wo, wdev
+
+    def bias_grad(self, n, G, gb, wo, wdev):
+        """a bias that feeds a BatchNorm has an identically zero gradient (the BN backward output sums to zero per
+        channel): its slice of the zero-initialised gradient buffer is simply never written"""
+        bn_fed = len(n.consumers) == 1 and n.consumers[0].op == 'bn' and n.act == linear
+        if not bn_fed:
+            self.prog.append(("bias_grad", lambda: wo.channel_sum(G, gb, False), None, wdev))
+
+    def transpose_once(self, tkey, d, w, wT):
+        """refresh the transposed weight copy wT unless this step's program already has"""
+        if tkey not in self.transposed:
+            self.transposed.add(tkey)
+            ops = self.ops
+            self.prog.append(("transpose_w", lambda: ops.transpose_weights(d, w, wT)))
+
+    def act_bwd(self, G, y, a):
+        ops = self.ops
+        self.prog.append(("act_bwd", lambda: ops.act_bwd(G, y, G, a.kind, a.alpha)))
+
+    # ---- the walk ------------------------------------------------------------------------------------
+    def lower(self, n):
+        if id(n) not in self.written or not self.req[id(n)]:
+            return
+        G = self.grad_of(n)
+        if n.op == 'input':
+            return
+        if n.op == 'concat':
+            return self.bwd_concat(n, G)
+        op = getattr(self, 'bwd_' + n.op, None)
+        if op is None:
+            raise NotImplementedError(n.op)
+        xin = n.inputs[0]
+        op(n, G, xin, self.sl(xin.out), self.sl(n.out), self.req[id(xin)])
+
+    def finish(self):
+        """the 3x3 -> 5x5 (-> fine 3x3) expansion of every collapsed layer's weight gradient: one launch for all layers, after
+        the last of them, on the lane the weight gradients run on"""
+        if not self.expands:
+            return
+        plan = self.plan
+        wo, wdev = (plan.side[1], plan.side[0]) if plan.side is not None else (self.ops, None)
+        tkey = ('expand', tuple(int(e[0].ptr) for e in self.expands))
+        tab = plan._scratch.setdefault('tables', {}).get(tkey)
+        if tab is None:
+            tab = plan._scratch['tables'][tkey] = wo.expand_table(self.expands)
+        self.prog.append(("expand_wgrad", lambda: wo.upconv_expand_batched(tab, False), None, wdev))
+        for dyl, fl, gw, N_, C_, K_, h_, w_ in self.frames:       # the frame's share of the fine weight gradients, on top
+            self.prog.append(("blconv_frame_wgrad", lambda dyl=dyl, fl=fl, gw=gw, N_=N_, C_=C_, K_=K_, h_=h_, w_=w_:
+                              wo.blconv_frame_wgrad(dyl, fl, gw, N_, C_, K_, h_, w_), None, wdev))
+        self.done(*self.expand_params)
+
+    # ---- one method per op: (node, its output gradient G, its input node, x, y, is the input's gradient wanted) ----
+    def bwd_concat(self, n, G):
+        ops, c0 = self.ops, 0
+        for i in n.inputs:
+            if (i.alias is None or i.alias[0] is not n) and self.req[id(i)]:
+                gi, acc = self.target(i)
+                src = G.channels(c0, c0 + i.shape[1])
+                self.prog.append(("concat_bwd_copy", lambda a=src, b=gi, acc=acc: ops.copy_view(a, b, acc)))
+                self.mark_written(i)
+            c0 += i.shape[1]
+
+    def bwd_convpool(self, n, G, xin, x, y, need_dx):
+        if n.act.kind in ('linear', 'relu', 'lrelu') and os.environ.get("GHM_POOL_READ_Y") is None:
+            y = None                    # the mask carries the sign of the pooled activation: its backward never reads it
+        mptr = n.aux['mask'] + self.n0 * int(np.prod(n.shape[1:]))       # (one mask byte per pooled element)
+        if not self.convpool_sparse(n, G, xin, x, y, need_dx, mptr):
+            Gf = self.convpool_mask_bwd(n, G, xin, x, y, need_dx, mptr)
+            self.conv_like(n, Gf, linear, xin, x, y, need_dx)
+
+    def convpool_sparse(self, n, G, xin, x, y, need_dx, mptr):
+        """the discriminator's first block (one input channel): both gradients straight from the pooled operands
+        (csrc/conv_pool_bwd.hip) -- the 537 MB full-resolution gradient is neither written nor read.  -> False: not served"""
+        plan, ops, st, prog, wgrad, a, l = self.plan, self.ops, self.st, self.prog, self.wgrad, n.act, n.layer
+        dS = plan._desc(n, x, plan._full(n, self.nb))
+        sparse = int(ops.pool_bwd_sparse_supported(dS, a.kind) or 0)
+        if not ((sparse & 1 or not wgrad) and (sparse & 2 or not need_dx) and sparse):
+            return False
+        if wgrad:
+            plan._grow_wgrad_ws(ops.pool_wgrad_sparse_workspace(dS))
+            gw, gb = st.grad(l.W), st.grad(l.b)
+            wo, wdev = self.fork()
+            prog.append(("conv_wgrad", lambda: wo.conv2d_pool_wgrad_sparse(dS, x, mptr, y, G, gw, gb, plan.wgrad_ws, a.kind, a.alpha, False),
+                         pool_sparse_meta(dS, WGRAD), wdev))
+            self.done(l.W, l.b)
+        if need_dx:
+            gi, acc = self.target(xin)
+            w = st.value(l.W)
+            dG = plan._desc(n, gi, plan._full(n, self.nb))        # the kernel strides dx by ITS sample stride, not x's
+            prog.append(("conv_dgrad", lambda: ops.conv2d_pool_dgrad_sparse(dG, mptr, y, G, w, gi, a.kind, a.alpha, acc),
+                         pool_sparse_meta(dG, DGRAD)))
+            self.mark_written(xin)
+        return True
+
+    def convpool_mask_bwd(self, n, G, xin, x, y, need_dx, mptr):
+        """-> the gradient of the conv's (never materialised in the forward pass) full-resolution output, from the arg-max
+        mask, the pooled value (sign -> activation derivative) and the pooled gradient; an ordinary conv backward follows"""
+        plan, ops, prog, cache, wgrad, a, nb = self.plan, self.ops, self.prog, self.cache, self.wgrad, n.act, self.nb
+        Gf = cache.get(('full', id(n)))
+        if Gf is None:
+            Gf = cache[('full', id(n))] = self.dev.empty((nb,) + tuple(n.aux['full_shape'][1:]))
+        # with the weight gradients wanted, the same pass also sums what it writes per channel: the bias gradient
+        gb = self.st.grad(n.layer.b) if wgrad else None
+        # who reads the full-resolution gradient: the conv's low-precision data / weight gradients read its q copy;
+        # the fp32 tensor is written only if a fp32 kernel reads it (thin first layer, geometries not served)
+        dF = plan._desc(n, x, Gf)
+        w_q = self.slq(xin.outq) is not None and plan._wq(dF)
+        d_lp = plan.use_q and need_dx and plan._lp(dF, DGRAD)
+        q_wanted = (wgrad and w_q) or d_lp
+        Gfq = None
+        if q_wanted and plan.q_epi and Gf.Cc % 8 == 0 and Gf.H % 2 == 0 and Gf.W % 4 == 0:
+            Gfq = self.gradq_of(n, Gf, pack=False)
+        if Gfq is None:
+            prog.append(("maxpool_mask_bwd", lambda: ops.maxpool2_mask_bwd(mptr, y, G, Gf, a.kind, a.alpha, gb, False)))
+            return Gf
+        # the full-resolution gradient (if anybody reads it) and its q copy in one pass
+        self.gq_ready.add(id(n))
+        Gf32 = None if ((w_q or not wgrad) and (d_lp or not need_dx)) else Gf
+        prog.append(("maxpool_mask_bwd", lambda: ops.maxpool2_mask_bwd_q(mptr, y, G, Gf32, Gfq, a.kind, a.alpha, gb, False)))
+        # the same gradient once more as half-width rows + column bits: the operand of the sparse matrix
+        # instruction, for the 5x5 weight gradient (DESIGN 4g; rows with a tied window row stay on the dense q copy)
+        if wgrad and w_q and ops.wgrad_pooled_split_supported(dF, self.dtype):
+            pc = cache.get(('pooled_c', id(n), nb))
+            if pc is None:
+                Kp, Hf, Wf = Gf.Cc, Gf.H, Gf.W
+                pc = cache[('pooled_c', id(n), nb)] = (
+                    QTensor.empty(self.dev, (nb, Kp, Hf, Wf // 2), self.dtype),
+                    self.dev.alloc(nb * (Kp // 8) * Hf * (Wf // 32) * 16 + 256), self.dev.alloc(nb * Hf * 4 + 256))
+            # (written by the stream that runs the weight gradient, its only reader: see conv_wgrad)
+            self.pooled_c[id(n)] = pc + (mptr, y, G, a)
+        return Gf
+
+    def conv_like(self, n, G, a, xin, x, y, need_dx):
+        """conv / deconv / dense, and the fused conv + pool behind its mask backward (G: the full-resolution gradient)"""
+        if a != linear and not self.is_pre(n):
+            self.act_bwd(G, y, a)
+        # conv input side = deconv output grad, output side = x
+        d = self.plan._desc(n, G, x) if n.op == 'deconv' else self.plan._desc(n, x, G)
+        if self.wgrad:
+            self.conv_wgrad(n, G, d, xin, x)
+        if need_dx:
+            self.conv_dgrad(n, G, xin, x)
+            self.mark_written(xin)
+
+    def bwd_conv(self, n, G, xin, x, y, need_dx):
+        self.conv_like(n, G, n.act, xin, x, y, need_dx)
+
+    bwd_deconv = bwd_dense = bwd_conv
+
+    def conv_wgrad(self, n, G, d, xin, x):
+        plan, prog, dt, l = self.plan, self.prog, self.dtype, n.layer
+        # the q copy of the output gradient, for the low-precision weight gradient (before its stream forks off)
+        xq = self.slq(xin.outq)
+        Gq = self.gradq_of(n, G) if (n.op in ('conv', 'convpool') and xq is not None and plan._wq(d)) else None
+        plan._need_wgrad_ws(d)
+        gw, gb = self.st.grad(l.W), self.st.grad(l.b)
+        wo, wdev = self.fork()
+        label = "%s_wgrad" % ('conv' if n.op == 'convpool' else n.op)
+        if Gq is not None and id(n) in self.pooled_c:
+            pc = self.pooled_c[id(n)]
+            prog.append(("maxpool_mask_compress", lambda: wo.maxpool2_mask_bwd_compress_q(
+                pc[3], pc[4], pc[5], pc[0], pc[1], pc[2], pc[6].kind, pc[6].alpha), None, wdev))
+            prog.append((label, lambda: wo.conv2d_wgrad_pooled_split(d, xq, Gq, pc[0], pc[1], pc[2], gw, plan.wgrad_ws, plan.dtype, False),
+                         sparse_meta(conv_meta(self.ops, d, WGRAD, dt)), wdev))
+        elif Gq is not None:
+            prog.append((label, lambda: wo.conv2d_wgrad_lp_q(d, xq, Gq, gw, plan.wgrad_ws, plan.dtype, False),
+                         conv_meta(self.ops, d, WGRAD, dt), wdev))
+        elif n.op == 'deconv':
+            prog.append((label, lambda: wo.conv2d_wgrad(d, G, x, gw, plan.wgrad_ws, False), conv_meta(self.ops, d, WGRAD), wdev))
+        elif n.op in ('conv', 'convpool') and plan._lp(d, WGRAD):
+            prog.append((label, lambda: wo.conv2d_wgrad_lp(d, x, G, gw, plan.wgrad_ws, plan.dtype, False),
+                         conv_meta(self.ops, d, WGRAD, dt), wdev))
+        else:
+            prog.append((label, lambda: wo.conv2d_wgrad(d, x, G, gw, plan.wgrad_ws, False), conv_meta(self.ops, d, WGRAD), wdev))
+        if n.op != 'convpool':          # convpool: summed by the mask backward pass
+            self.bias_grad(n, G, gb, wo, wdev)
+        self.done(l.W, l.b)
+
+    def conv_dgrad(self, n, G, xin, x):
+        plan, ops, st, prog, l = self.plan, self.ops, self.st, self.prog, n.layer
+        w = st.value(l.W)
+        gi, acc = self.target(xin)
+        convish = n.op in ('conv', 'convpool')
+        # the producer's own nonlinearity (a conv -> LeakyRectify -> conv chain without BatchNorm: the
+        # PatchGAN, p2p.py:285-286) differentiated in THIS data gradient's epilogue instead of a separate
+        # read-modify-write pass over the gradient tensor
+        form = 0
+        if (not acc and convish and xin.op in ('conv', 'deconv', 'dense')
+                and xin.act.kind in ('relu', 'lrelu') and len(xin.consumers) == 1 and not self.is_pre(xin)):
+            form = ops.dgrad_dact_supported(plan._desc(n, gi, G), self.dtype) or 0
+        if form:
+            return self.conv_dgrad_dact(n, G, xin, x, gi, acc, w, form)
+        if n.op == 'deconv':
+            d = plan._desc(n, G, gi)
+            prog.append(("deconv_dgrad", lambda: ops.conv2d_fwd(d, G, w, None, gi, 'linear', 0.0, acc), conv_meta(ops, d, FWD)))
+            return
+        d = plan._desc(n, gi, G)
+        label = "%s_dgrad" % ('conv' if n.op == 'convpool' else n.op)
+        if convish and plan._lp(d, DGRAD):
+            wqT = plan._lp_pack_entry(prog, d, w, ('w', id(l.W)), True, self.transposed)
+            Gq = self.gradq_of(n, G)
+            if Gq is not None:
+                giq = self.fused_gq(xin, gi, acc) if ops.lp_q_direct(d, DGRAD, self.dtype) else None
+                if giq is None:
+                    self.gq_ready.discard(id(xin))
+                prog.append((label, lambda: ops.conv2d_dgrad_lp_q(d, Gq, wqT, gi, giq, plan.dtype, None, 'linear', 0.0, acc),
+                             conv_meta(ops, d, DGRAD_T, self.dtype,
+                                       extra=(" +q" if giq is not None else "") + (" +acc" if acc else ""))))
+            else:
+                prog.append((label, lambda: ops.conv2d_dgrad_lp(d, G, wqT, gi, plan.dtype, None, 'linear', 0.0, acc),
+                             conv_meta(ops, d, DGRAD_T, self.dtype)))
+        elif convish and plan._use_dgrad_t(d, l.W):
+            # data gradient as a forward-form conv on the transposed weights (LDS-patch kernels)
+            wT = st.transposed(l.W)
+            self.transpose_once(id(l.W), d, w, wT)
+            prog.append((label, lambda: ops.conv2d_dgrad_t(d, G, wT, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, DGRAD_T)))
+        else:
+            prog.append((label, lambda: ops.conv2d_dgrad(d, G, w, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, DGRAD)))
+
+    def conv_dgrad_dact(self, n, G, xin, x, gi, acc, w, form):
+        """the data gradient with the producer's relu / leaky relu differentiated in its epilogue; ``form`` (what the library
+        serves): 1 = on the weights as stored, 2 = on their transposed copy, 3 = on the low-precision transposed pack"""
+        plan, ops, prog, l, xa = self.plan, self.ops, self.prog, n.layer, xin.act
+        d = plan._desc(n, gi, G)
+        dt = 'f32'
+        if form == 1:
+            wsel = w
+        elif form == 2:
+            wsel = self.st.transposed(l.W)
+            self.transpose_once(id(l.W), d, w, wsel)
+        else:
+            wsel, dt = plan._lp_pack_entry(prog, d, w, ('w', id(l.W)), True, self.transposed), self.dtype
+        xin.aux[('grad_is_pre', self.key)] = True
+        Gq = self.gradq_of(n, G) if form == 3 else None
+        if Gq is None or not (ops.lp_q_direct(d, DGRAD, self.dtype) or self.dtype in SPLITS):
+            prog.append(("conv_dgrad", lambda: ops.conv2d_dgrad_dact(d, G, wsel, gi, x, xa.kind, xa.alpha, dt),
+                         conv_meta(ops, d, DGRAD_T if form != 1 else DGRAD, dt)))
+            return
+        giq = self.fused_gq(xin, gi, acc) if ops.lp_q_direct(d, DGRAD, self.dtype) else None
+        # split modes: the slope from the sign of the producer's q copy (2 bytes per element, and the
+        # producer's fp32 activation need not exist: _act_fp32_dropped)
+        ysrc = x
+        if self.dtype in SPLITS and xin.outq is not None and gi.Cc % 8 == 0 and not os.environ.get("GHM_DACT_FP32"):
+            ysrc = self.slq(xin.outq)
+        prog.append(("conv_dgrad", lambda: ops.conv2d_dgrad_dact_lp_q(d, Gq, wsel, gi, giq, ysrc, xa.kind, xa.alpha, plan.dtype),
+                     conv_meta(ops, d, DGRAD_T, dt, extra=" +dact" + (" +q" if giq is not None else ""))))
+
+    def bwd_upconv(self, n, G, xin, x, y, need_dx):
+        if self.nslice is not None:
+            raise NotImplementedError("sample slices through a collapsed up-sample convolution")
+        if n.act != linear:
+            self.act_bwd(G, y, n.act)
+        d = self.plan._upconv_desc(n, x)
+        C, K = x.Cc, n.shape[1]
+        G4 = G.reshape((x.N, 4 * K, x.H, x.W))
+        G4q_w = self.gradq_of(n, G4) if (self.wgrad and xin.outq is not None and self.plan._wq(d)) else None
+        bl = n.attrs.get('mode') == 1
+        if bl:      # the six border lines of the fine gradient, for both frame gradients (before the gradient stream forks)
+            ops = self.ops
+            self.prog.append(("blconv_frame_gather", lambda dyl=n.aux['dyl']: ops.blconv_frame_gather(G4, C, K, dyl)))
+        if self.wgrad:
+            self.upconv_wgrad(n, G, G4, G4q_w, d, xin, x)
+        if need_dx:
+            self.upconv_dgrad(n, G4, d, xin)
+            self.mark_written(xin)
+
+    def upconv_wgrad(self, n, G, G4, G4q, d, xin, x):
+        plan, ops, prog, dt, l = self.plan, self.ops, self.prog, self.dtype, n.layer
+        C, K, xq, dwpc = x.Cc, n.shape[1], xin.outq, n.aux['dwpc']
+        bl = n.attrs.get('mode') == 1
+        label = ('blconv' if bl else 'upconv') + "_wgrad"
+        plan._need_wgrad_ws(d)
+        gw, gb = self.st.grad(l.W), self.st.grad(l.b)
+        wo, wdev = self.fork()
+        if G4q is not None and plan._bl_skip(n, d, WGRAD):
+            prog.append((label, lambda: wo.blconv_wgrad_split(d, xq, G4q, dwpc, plan.wgrad_ws, plan.dtype, False),
+                         bl_meta(conv_meta(ops, d, WGRAD, dt)), wdev))
+        elif G4q is not None:
+            prog.append((label, lambda: wo.conv2d_wgrad_lp_q(d, xq, G4q, dwpc, plan.wgrad_ws, plan.dtype, False),
+                         conv_meta(ops, d, WGRAD, dt), wdev))
+        elif plan._lp(d, WGRAD):
+            prog.append((label, lambda: wo.conv2d_wgrad_lp(d, x, G4, dwpc, plan.wgrad_ws, plan.dtype, False),
+                         conv_meta(ops, d, WGRAD, dt), wdev))
+        else:
+            prog.append((label, lambda: wo.conv2d_wgrad(d, x, G4, dwpc, plan.wgrad_ws, False), conv_meta(ops, d, WGRAD), wdev))
+        self.expands.append((dwpc, gw, C, K, n.attrs.get('mode', 0)))      # expanded to l.W's gradient by finish()
+        if bl:
+            self.frames.append((n.aux['dyl'], n.aux['fl'], gw, x.N, C, K, x.H, x.W))
+        self.bias_grad(n, G, gb, wo, wdev)
+        self.done(l.b)                              # l.W: written by the batched expansion
+        self.expand_params.append(l.W)
+
+    def upconv_dgrad(self, n, G4, d, xin):
+        plan, ops, prog, dt, l = self.plan, self.ops, self.prog, self.dtype, n.layer
+        C, K, wpc, wpcT = d.C, n.shape[1], n.aux['wpc'], n.aux['wpcT']
+        bl = n.attrs.get('mode') == 1
+        label = ('blconv' if bl else 'upconv') + "_dgrad"
+        gi, acc = self.target(xin)
+        if plan._lp(d, DGRAD):
+            wqT = plan._lp_pack_entry(prog, d, wpc, ('c', id(l.W)), True, self.transposed)
+            G4q = self.gradq_of(n, G4)
+            if G4q is not None and plan._bl_skip(n, d, DGRAD):
+                prog.append((label, lambda: ops.blconv_dgrad_split(d, G4q, wqT, gi, plan.dtype, acc),
+                             bl_meta(conv_meta(ops, d, DGRAD_T, dt))))
+            elif G4q is not None:
+                prog.append((label, lambda: ops.conv2d_dgrad_lp_q(d, G4q, wqT, gi, None, plan.dtype, None, 'linear', 0.0, acc),
+                             conv_meta(ops, d, DGRAD_T, dt)))
+            else:
+                prog.append((label, lambda: ops.conv2d_dgrad_lp(d, G4, wqT, gi, plan.dtype, None, 'linear', 0.0, acc),
+                             conv_meta(ops, d, DGRAD_T, dt)))
+        elif C > 4 and ops.dgrad_t_supported(d):
+            self.transpose_once(('c', id(l.W)), d, wpc, wpcT)
+            prog.append((label, lambda: ops.conv2d_dgrad_t(d, G4, wpcT, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, DGRAD_T)))
+        else:
+            prog.append((label, lambda: ops.conv2d_dgrad(d, G4, wpc, gi, None, 'linear', 0.0, acc), conv_meta(ops, d, DGRAD)))
+        if bl:
+            prog.append(("blconv_frame_dgrad", lambda dyl=n.aux['dyl'], w3=self.st.value(l.W): ops.blconv_frame_dgrad(dyl, w3, gi, K)))
+
+    def bwd_dropout(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            gi, acc = self.target(xin)
+            if acc or self.nslice is not None:
+                raise NotImplementedError("DropoutLayer input with several consumers / sample slices")
+            # same key, same counter value as the forward pass of this step -> the same mask
+            ops = self.ops
+            self.prog.append(("dropout_bwd", lambda p=n.attrs['p'], k=n.aux['key'], c=self.plan.rng_counter: ops.dropout(G, gi, p, k, c)))
+            self.mark_written(xin)
+
+    def bwd_pp_to_hi(self, n, G, xin, x, y, need_dx):
+        if need_dx and self.nslice is None and self.plan._bn_hi(xin) and G.nstride % 2 == 0:
+            # the BatchNorm backward reads this gradient through the inverse permutation: no hi_to_pp pass
+            self.grads[id(xin)] = G
+            self.hi_grads.add(id(xin))
+            self.mark_written(xin)
+        elif need_dx:
+            gi, acc = self.target(xin)
+            if acc or self.nslice is not None:
+                raise NotImplementedError("parity-planar tensor with several consumers / sample slices")
+            ops = self.ops
+            self.prog.append(("hi_to_pp", lambda: ops.hi_to_pp(G, gi)))
+            self.mark_written(xin)
+
+    def bn_input_q(self, n, xin, gi, acc):
+        """-> (q tensor the BatchNorm backward's apply pass writes beside the input gradient gi, or None; is the fp32 gi
+        written too).  The convolution in front of this BatchNorm reads gi as the operand of its low-precision data / weight
+        gradients: the apply pass writes the q copy itself -- and no fp32 gradient at all when both read q"""
+        plan = self.plan
+        if not (plan.q_epi and not acc and self.nslice is None and plan.bn_groups == 1 and not n.instance
+                and xin.op in ('conv', 'upconv') and len(xin.consumers) == 1 and xin.act == linear and gi.HW % 2 == 0
+                and gi.Cc % 8 == 0 and gi.nstride % 2 == 0):
+            return None, True
+        xx = xin.inputs[0]
+        if xin.op == 'conv':
+            dq, gview = plan._desc(xin, xx.out, gi), gi
+        else:
+            dq = plan._upconv_desc(xin, xx.out)
+            gview = gi.reshape((xx.out.N, 4 * xin.shape[1], xx.out.H, xx.out.W))
+        w_q = xx.outq is not None and plan._wq(dq)
+        d_q = plan._lp(dq, DGRAD) or not self.req[id(xx)]
+        if not ((w_q or not self.wgrad) and (plan._lp(dq, DGRAD) or w_q)):
+            return None, True
+        giq = self.gradq_of(xin, gview, pack=False).reshape(gi.shape)
+        self.gq_ready.add(id(xin))
+        return giq, not ((w_q or not self.wgrad) and d_q) or xin.attrs.get('mode') == 1     # (the frame reads its border lines)
+
+    def bwd_bn(self, n, G, xin, x, y, need_dx):
+        plan, ops, st, prog, cache, a, l = self.plan, self.ops, self.st, self.prog, self.cache, n.act, n.layer
+        # (the backward kernels recompute y = act(bn(x)) from x instead of reading the output tensor: bit-identical
+        # to the forward value, one tensor less to read in both of their passes)
+        gam, bet = st.value(l.gamma), st.value(l.beta)
+        if self.wgrad:
+            dg, db = st.grad(l.gamma), st.grad(l.beta)
+        else:
+            C = n.shape[1]
+            dg, db = plan._bn_scratch.channels(0, C), plan._bn_scratch.channels(C, 2 * C)
+        gi, acc = self.target(xin)
+        dst = gi
+        if acc:
+            dst = self.dev.empty(gi.shape) if ('bn_tmp', id(n)) not in cache else cache[('bn_tmp', id(n))]
+            cache[('bn_tmp', id(n))] = dst
+        giq, gi32 = self.bn_input_q(n, xin, gi, acc)
+        m, iv = n.aux['mean'], n.aux['inv']
+        if n.instance:
+            if self.nslice is not None:
+                raise NotImplementedError("InstanceNorm backward on a sample slice")
+            prog.append(("in_bwd", lambda grp=n.aux['group']: ops.instance_norm_bwd(G, x, dst, m, iv, gam, bet, dg, db, plan.bn_ws,
+                                                                                   a.kind, a.alpha, False, grp)))
+        elif id(n) in self.hi_grads:
+            dst32 = dst if (giq is None or gi32) else None
+            prog.append(("bn_bwd", lambda: ops.bn_backward_hi(G, x, dst32, giq, m, iv, gam, bet, dg, db, plan.bn_ws, a.kind, a.alpha, False)))
+        elif giq is not None:
+            dst32 = dst if gi32 else None
+            prog.append(("bn_bwd", lambda: ops.bn_backward_q(G, None, x, dst32, m, iv, gam, dg, db, plan.bn_ws, giq, a.kind, a.alpha,
+                                                             False, bet)))
+        elif plan.bn_groups == 2:
+            hb = plan.batch // 2
+            halves = (0, 1)
+            if self.nslice is not None:
+                halves = (self.n0 // hb,) if (self.nb == hb and self.n0 % hb == 0) else None
+            if halves is None:
+                raise NotImplementedError("sample slice that is not one half of a [real | fake] batch")
+            for idx, h in enumerate(halves):
+                sub = (lambda t, h=h: t.samples(h * hb, (h + 1) * hb)) if self.nslice is None else (lambda t: t)
+                # the second half adds to dgamma / dbeta
+                prog.append(("bn_bwd", lambda G=sub(G), x=sub(x), dst=sub(dst), m=n.aux['mean_g'][h], iv=n.aux['inv_g'][h], awh=idx > 0:
+                             ops.bn_backward_x(G, x, dst, m, iv, gam, bet, dg, db, plan.bn_ws, a.kind, a.alpha, awh)))
+        else:
+            prog.append(("bn_bwd", lambda: ops.bn_backward_x(G, x, dst, m, iv, gam, bet, dg, db, plan.bn_ws, a.kind, a.alpha, False)))
+        if acc:
+            prog.append(("bn_bwd_acc", lambda: ops.copy_view(dst, gi, True)))
+        self.done(l.gamma, l.beta)
+        self.mark_written(xin)
+
+    def bwd_act(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            gi, acc = self.target(xin)
+            ops, a = self.ops, n.act
+            self.prog.append(("act_bwd", lambda: ops.act_bwd(G, y, gi, a.kind, a.alpha, acc)))
+            self.mark_written(xin)
+
+    def bwd_reshape(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            if id(xin) in self.grads or id(xin) in self.cache or xin.alias is not None:
+                gi, acc = self.target(xin)
+                ops = self.ops
+                self.prog.append(("reshape_bwd", lambda: ops.copy_view(G.reshape(gi.shape), gi, acc)))
+            else:
+                self.grads[id(xin)] = self.cache[id(xin)] = G.reshape((self.nb,) + tuple(xin.shape[1:]))
+            self.mark_written(xin)
+
+    def bwd_up_nearest(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            gi, acc = self.target(xin)
+            fn = self.ops.upsample_nearest2_bwd if n.op == 'up_nearest' else self.ops.upsample_bilinear2_bwd
+            self.prog.append(("%s_bwd" % n.op, lambda: fn(G, gi, acc)))
+            self.mark_written(xin)
+
+    bwd_up_bilinear = bwd_up_nearest
+
+    def bwd_maxpool(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            gi, acc = self.target(xin)
+            if acc:
+                raise NotImplementedError("maxpool input with several consumers")
+            fa = linear
+            if xin.op in ('conv', 'deconv', 'dense') and len(xin.consumers) == 1 and xin.act.kind in ('lrelu', 'relu'):
+                # fold the producer's LeakyReLU/ReLU backward into the pooling scatter (mask from the output sign)
+                fa = xin.act
+                xin.aux[('grad_is_pre', self.key)] = True
+            ops = self.ops
+            self.prog.append(("maxpool_bwd", lambda: ops.maxpool2_bwd(x, y, G, gi, fa.kind, fa.alpha)))
+            self.mark_written(xin)
+
+    def bwd_avgpool(self, n, G, xin, x, y, need_dx):
+        if need_dx:
+            gi, acc = self.target(xin)
+            if acc:
+                raise NotImplementedError("avgpool input with several consumers")
+            ops = self.ops
+            self.prog.append(("avgpool_bwd", lambda p=n.attrs['p']: ops.avgpool_bwd(G, gi, p)))
+            self.mark_written(xin)
 
 
 def conv_meta(ops, d, kind, dtype='f32', pooled=False, extra='', moved=None):
@@ -1543,12 +1651,12 @@ def conv_meta(ops, d, kind, dtype='f32', pooled=False, extra='', moved=None):
     if pooled:
         name = ("sp_conv2_kernel<%d, %d> fwd+pool" % (d.kh, d.stride)) if dtype in SPLITS else \
             ("lp_conv_kernel<%s, %d, %d>" % (dtype, d.kh, d.stride)) if dtype != 'f32' else \
-            ("fanout_kernel<fwd+pool>" if d.C <= 4 else ops.conv_variant(d, 0).split(" splits")[0])   # same kernel, pooled epilogue
+            ("fanout_kernel<fwd+pool>" if d.C <= 4 else ops.conv_variant(d, FWD).split(" splits")[0])   # same kernel, pooled epilogue
     elif dtype != 'f32':
-        fam = "wgrad" if kind == 2 else ("dgrad_s2" if kind in (1, 3) and d.stride == 2 else "conv")
+        fam = "wgrad" if kind == WGRAD else ("dgrad_s2" if kind in (DGRAD, DGRAD_T) and d.stride == 2 else "conv")
         name = "lp_%s_kernel<%s, %d, %d>" % (fam, dtype, d.kh, d.stride)
         if hasattr(ops, 'conv_variant_lp'):         # (small maps run their own kernel family behind the same entry points)
-            name = ops.conv_variant_lp(d, {0: 0, 1: 1, 3: 1, 2: 2}[kind], dtype)
+            name = ops.conv_variant_lp(d, DGRAD if kind == DGRAD_T else kind, dtype)
     else:
         name = ops.conv_variant(d, kind)
     # algorithmic HBM bytes of the launch (the wide tensor(s) once): conv input + conv output, fp32; a fused
@@ -1596,7 +1704,7 @@ def pool_sparse_meta(d, kind):
     pooled gradient + pooled activation (fp32) + mask (1 B) per pooled element (+ the thin tensor), flops = the 25
     multiply-adds per pooled value the gather does (a quarter of the dense convolution's)"""
     pooled = float(d.N) * d.K * (d.H // 2) * (d.W // 2)
-    return {"kernel": "pool_thin_wgrad_kernel" if kind == 2 else "pool_thin_dgrad_kernel", "dtype": 'f32',
+    return {"kernel": "pool_thin_wgrad_kernel" if kind == WGRAD else "pool_thin_dgrad_kernel", "dtype": 'f32',
             "bytes": 9.0 * pooled + 4.0 * d.N * d.C * d.H * d.W, "thin": True, "flops": 2.0 * pooled * d.kh * d.kw,
             "geom": "N%d C%d %dx%d K%d k%d s%d" % (d.N, d.C, d.H, d.W, d.K, d.kh, d.stride)}
 
