@@ -9,6 +9,7 @@ from gan_heightmaps_amd._lib import tuning_env
 
 from oracle import lp as LP
 from oracle import ops as O
+from tests import elementwise_q_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -431,6 +432,74 @@ def test_pool_upsample_act(gpu):
         g = rng.randn(*x.shape).astype(np.float32)
         ops.act_bwd(dev.tensor(g), yd2, dxd, act, alpha)
         assert rel(dxd.numpy(), df(y_ref, g)) < 1e-4
+    # relu / lrelu / linear as well; an HW % 4 != 0 shape (the VEC = 1 kernels); channel-slice views; act_bwd(accumulate=True)
+    for shape, _ in R.VIEW_ROWS:
+        d = R.view_inputs(shape)
+        for sliced in (False, True):
+            for act, alpha in [('relu', 0.0), ('lrelu', 0.2), ('linear', 0.0), ('sigmoid', 0.0), ('tanh', 0.0)]:
+                xv = _CanaryView(gpu, shape, sliced, d['x'])
+                yv = _CanaryView(gpu, shape, sliced)
+                ops.act_fwd(xv.t, yv.t, act, alpha)
+                y32 = yv.t.numpy()
+                y_ref = R.act_fwd(d['x'], act, alpha)
+                assert rel(y32, y_ref) < TOL and yv.stray().size == 0, (shape, sliced, act)
+                if act in ('relu', 'lrelu', 'linear'):      # one rounding at most
+                    assert R.worst(y32, y_ref, np.abs(y_ref)) <= 2, (shape, sliced, act)
+                gv = _CanaryView(gpu, shape, sliced, d['g'])
+                dv = _CanaryView(gpu, shape, not sliced, d['prev'])      # (the three sample strides differ)
+                ops.act_bwd(gv.t, yv.t, dv.t, act, alpha)
+                inc = dv.t.numpy()
+                dref = d['g'].astype(np.float64) * R.dact_from_out(y32, act, alpha)
+                assert rel(inc, dref) < TOL and dv.stray().size == 0, (shape, sliced, act)
+                dv.t.set(d['prev'])
+                ops.act_bwd(gv.t, yv.t, dv.t, act, alpha, accumulate=True)
+                acc = dv.t.numpy()
+                if act in ('relu', 'linear'):       # the slope is 0 or 1: the product is exact, fused with the sum or not
+                    assert R.bits_equal(acc, (d['prev'] + inc).astype(np.float32)), (shape, sliced, act)
+                elif act == 'lrelu':                # a product and a sum (one rounding when the compiler fuses them) -> k = 3
+                    assert R.worst(acc, d['prev'] + dref, np.abs(d['prev']) + np.abs(dref)) <= 3, (shape, sliced, act)
+                assert rel(acc, d['prev'] + dref) < TOL and dv.stray().size == 0, (shape, sliced, act)
+                assert xv.stray().size == 0 and gv.stray().size == 0
+                for v in (xv, yv, gv, dv):
+                    dev.free(v.ptr)
+
+
+class _CanaryView:
+    """an fp32 tensor (contiguous, or the middle channels of a tensor one channel wider on both sides) in an allocation filled
+    with a NaN canary, a tail behind it included"""
+
+    def __init__(self, gpu, shape, sliced, data=None):
+        self.dev, _, D = gpu
+        N, C, H, W = shape
+        HW = H * W
+        ns, el0 = ((C + 2) * HW, HW) if sliced else (C * HW, 0)
+        self.total = N * ns + HW
+        self.ptr = self.dev.alloc(4 * self.total)
+        R.canary_fill(self.dev, self.ptr, 4 * self.total)
+        self.t = D.DevTensor(self.dev, self.ptr + 4 * el0, shape, ns)
+        self.inside = R.f32_inside(N, ns, el0, C * HW, self.total)
+        if data is not None:
+            self.t.set(data)
+
+    def stray(self):
+        return R.canary_changed(self.dev, self.ptr, 4 * self.total, self.inside)
+
+
+@pytest.mark.parametrize("accumulate", [False, True])
+@pytest.mark.parametrize("dst_sliced", [False, True])
+@pytest.mark.parametrize("src_sliced", [False, True])
+@pytest.mark.parametrize("shape", [s for s, _ in R.VIEW_ROWS], ids=str)
+def test_copy_view(gpu, shape, src_sliced, dst_sliced, accumulate):
+    """ghm_copy_view: VEC = 4 (HW % 4 == 0) and VEC = 1, contiguous tensors and channel slices (differing sample strides),
+    plain and accumulating; exact, and nothing outside the destination view is written"""
+    dev, ops, D = gpu
+    d = R.view_inputs(shape)
+    src, dst = _CanaryView(gpu, shape, src_sliced, d['x']), _CanaryView(gpu, shape, dst_sliced, d['prev'])
+    ops.copy_view(src.t, dst.t, accumulate=accumulate)
+    want = (d['prev'] + d['x']).astype(np.float32) if accumulate else d['x']
+    assert R.bits_equal(dst.t.numpy(), want)
+    assert dst.stray().size == 0 and src.stray().size == 0 and R.bits_equal(src.t.numpy(), d['x'])
+    dev.free(src.ptr), dev.free(dst.ptr)
 
 
 def test_losses_and_optimizers(gpu):
