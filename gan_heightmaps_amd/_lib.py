@@ -163,6 +163,10 @@ SIGNATURES = {
     "ghm_texture_finalize": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_terrain_seed": [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_terrain_emit": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "ghm_world_seed": [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
+    "ghm_world_emit": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "ghm_world_crop": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32],
+    "ghm_world_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_lsgan_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_bce_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_recon_loss": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _f, _i32],

@@ -391,6 +391,11 @@ def conv_desc(N, Cc, H, W, K, kh, kw, stride, pad, x_nstride=None, y_nstride=Non
 OPT_RULES = {'sgd': 0, 'momentum': 1, 'nesterov_momentum': 2, 'adagrad': 3, 'adadelta': 4, 'adamax': 5, 'amsgrad': 6}
 
 
+class WorldTile(C.Structure):
+    """ghm_world_tile (include/ghm.h)"""
+    _fields_ = [("chunk", C.c_void_p * 4), ("y0", C.c_int32), ("x0", C.c_int32)]
+
+
 def _vp(x):
     if x is None:
         return C.c_void_p(0)
@@ -1027,6 +1032,37 @@ class Ops:
         assert src.N == 1
         call("ghm_terrain_emit", self.h, _vp(src), src.Cc, src.H, src.W, r0, n, int(out_u8), int(grey),
              C.c_void_p(int(out_ptr)))
+
+    # regions of an unbounded world (csrc/world.hip, gan_heightmaps_amd/world.py)
+    def world_seed(self, P, ci0, cj0, ncy, ncx, s, y0, x0, blend, dst):
+        """the seed rectangle [y0, y0 + dst.H) x [x0, x0 + dst.W) of the unbounded canvas -> dst [1, C, rows, cols]; P
+        [ncy ncx, C s s] holds the head maps of the cell block [ci0, ci0 + ncy) x [cj0, cj0 + ncx)"""
+        C = dst.Cc
+        assert P.N == ncy * ncx and P.Cc * P.HW == C * s * s and dst.N == 1
+        call("ghm_world_seed", self.h, _vp(P), P.nstride, ci0, cj0, ncy, ncx, C, s, y0, x0, dst.H, dst.W, int(blend),
+             _vp(dst), dst.nstride)
+
+    def world_emit(self, src, r0, c0, K, chunk_ptr):
+        """rows [r0, r0 + K) x columns [c0, c0 + K) of src [1, C, H, W] -> fp32 [C, K, K] at chunk_ptr"""
+        assert src.N == 1
+        call("ghm_world_emit", self.h, _vp(src), src.Cc, src.H, src.W, r0, c0, K, C.c_void_p(int(chunk_ptr)))
+
+    def world_crop(self, chunk_ptr, Cc, K, r0, c0, nr, nc, out_u8, grey, out_ptr, pitch, xoff):
+        """rows [r0, r0 + nr) x columns [c0, c0 + nc) of a chunk [Cc, K, K] -> columns [xoff, xoff + nc) of the staging
+        buffer at out_ptr (rows of ``pitch`` pixels): fp32 [Cc, nr, pitch] or uint8 [nr, pitch] / [nr, pitch, 3]"""
+        call("ghm_world_crop", self.h, C.c_void_p(int(chunk_ptr)), Cc, K, r0, c0, nr, nc, int(out_u8), int(grey),
+             C.c_void_p(int(out_ptr)), pitch, xoff)
+
+    def world_gather(self, tiles, K, dst):
+        """tiles: [((p00, p01, p10, p11), y0, x0)] -- chunk pointers [Cc, K, K] (0 where the tile does not reach) and the
+        tile's origin in the first -> dst [B, Cc, T, T]; slots past len(tiles) repeat the last tile"""
+        tab = (WorldTile * len(tiles))()
+        for t, (ptrs, y0, x0) in zip(tab, tiles):
+            for i, p in enumerate(ptrs):
+                t.chunk[i] = int(p)
+            t.y0, t.x0 = y0, x0
+        assert dst.H == dst.W
+        call("ghm_world_gather", self.h, tab, len(tiles), dst.N, dst.Cc, dst.H, K, _vp(dst), dst.nstride)
 
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous

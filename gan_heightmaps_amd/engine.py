@@ -58,6 +58,7 @@ class ParamStore:
         self.g = dev.zeros((1, self.n_pad, 1, 1))
         self.s = dev.zeros((1, max(ns, 1), 1, 1))
         self.opt_state = {}
+        self.version = 0            # counts uploads: a host write to any parameter (set_value, load_model) moves it
         for p in self.params:
             p.store = self
             self.upload(p)
@@ -87,6 +88,7 @@ class ParamStore:
         return flat.reshape(p.shape).copy()
 
     def upload(self, p):
+        self.version += 1
         self.value(p).set(self._to_device_layout(p, p.value))
 
     def download(self, p):

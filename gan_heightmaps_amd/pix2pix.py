@@ -144,6 +144,21 @@ class Pix2Pix:
         return generate_terrain(self.engine, self.dcgan['gen'], self.latent_dim, self.sampler, self.is_a_grayscale,
                                 grid=grid, z=z, blend=blend, band=band, out=out, uint8=uint8, deterministic=deterministic)
 
+    def terrain_world(self, seed, **kw):
+        """An unbounded terrain of this model addressed by pixel coordinates: a TerrainWorld whose ``heightmap`` /
+        ``texture`` / ``both`` (y0, x0, h, w) return any rectangle of the world of ``seed``, negative coordinates included.
+        A pixel is a pure function of (weights, seed, coordinates): requests made at different times, in any order, agree
+        bit for bit where they overlap.  The world is cut into chunks of ``chunk_cells`` generator outputs a side, each from
+        one trunk pass over a world-anchored seed window with an exact halo; chunks are cached in HBM (``cache_mb``) and
+        recomputed after the parameters change; textures are world-anchored U-Net tiles gathered on the device
+        (gan_heightmaps_amd/world.py).  Not in the reference.
+        kw: chunk_cells (default: a fixed memory budget; part of the world's identity), blend ('bilinear' | 'mosaic'),
+        overlap (texture tiles, default in_shp / 4), batch_size (tiles per pass), cache_mb, latent_fn(i, j) -> [latent_dim]
+        in place of the seeded sampler draw.  Use it as a context manager, or close() it.  Leaves the training state
+        untouched."""
+        from .world import TerrainWorld
+        return TerrainWorld(self, seed, **kw)
+
     def _is_writer(self):
         """files (results.txt, PNG dumps, checkpoints) are written by rank 0 only; every rank still runs the
         forward passes and iterator draws of the per-epoch dumps, which are part of the training trajectory"""

@@ -202,6 +202,13 @@ class GanStep:
         self._built = {}
         self._infer = {}
         self._subgraph = {}
+        self._param_ticks = 0
+
+    @property
+    def param_version(self):
+        """moves whenever parameters or BatchNorm running statistics may have changed on the device: every train / loss /
+        non-deterministic forward call issued and every host write to a parameter (world.py keys its chunk cache on it)"""
+        return self._param_ticks + sum(st.version for st in self.stores.values())
 
     def loss_scale_state(self):
         """[{scale, clean_steps, skipped_steps}] per stage stream (fp16 mode; [] otherwise).  Synchronises."""
@@ -251,6 +258,7 @@ class GanStep:
         zero: exact, and it needs no further collective in the C ABI."""
         if self.comm is None or self.world == 1:
             return
+        self._param_ticks += 1
         self.sync()
         for k in ('dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_disc'):
             st = self.stores[k]
@@ -989,6 +997,7 @@ class GanStep:
         return self._read_losses()
 
     def _run_loss(self, b):
+        self._param_ticks += 1                  # loss_fn still updates the BatchNorm running statistics
         if self.use_graph == 'recorded':
             self._run_recorded(b, 'loss')
         else:
@@ -1045,6 +1054,7 @@ class GanStep:
 
     def enqueue_train(self, b, wrap=None):
         """one train step on the data already resident in b.z / b.x / b.y (asynchronous)"""
+        self._param_ticks += 1
         if self.use_graph == 'recorded':
             return self._run_recorded(b, 'train', wrap)
         if self.exchange:
@@ -1070,6 +1080,7 @@ class GanStep:
     def profile_train(self, B):
         """[(label, ms, meta)] per program entry, stream by stream (synchronising; mutates parameters like a
         real step: compute, then the exchange, then the updates)."""
+        self._param_ticks += 1
         b = self.built(B)
         out = []
 
@@ -1123,6 +1134,7 @@ class GanStep:
     def generate(self, key, inp, deterministic=False):
         inp = np.ascontiguousarray(inp, np.float32)
         plan, prog = self._infer_plan(key, inp.shape[0], deterministic)
+        self._param_ticks += not deterministic  # batch statistics move the running ones
         self.sync()
         plan.input_nodes[0].out.set(inp)
         for e in prog:
@@ -1135,6 +1147,7 @@ class GanStep:
         Z = np.ascontiguousarray(Z, np.float32)
         pg, prog_g = self._infer_plan('dcgan_gen', Z.shape[0], deterministic)
         pu, prog_u = self._infer_plan('p2p_gen', Z.shape[0], deterministic)
+        self._param_ticks += not deterministic
         self.sync()
         pg.input_nodes[0].out.set(Z)
         for e in prog_g:
