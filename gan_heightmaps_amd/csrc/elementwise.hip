@@ -1638,6 +1638,7 @@ int ghm_image_batch(ghm_ctx* ctx, const uint8_t* src_nhwc, int32_t N, int32_t H,
 
 int ghm_rmsprop(ghm_ctx* ctx, float* p, const float* g, float* acc, int64_t n, const float* hyper, float rho, float eps,
                 float grad_scale) {
+    GHM_CHECK(aligned16(p) && aligned16(g) && aligned16(acc), "ghm_rmsprop: p, g and acc must be 16-byte aligned");
     if (n == 0) return 0;
     hipLaunchKernelGGL(rmsprop_kernel, EW_GRID((n + 3) / 4), p, g, acc, (long)n, hyper, rho, eps, grad_scale,
                        (const float*)ctx->ls_state);

@@ -1,20 +1,24 @@
 """The seven lasagne.updates rules of csrc/optim.hip (ghm_opt_update) on the MI355X: the kernels against float64
 restatements of the rules (written from Lasagne's definitions, below), the fp16 loss-scale contract, whole train steps
-through Pix2Pix against the oracle's float64 gradients, and the sharded (rs_ag) update path against the flat one."""
+through Pix2Pix against the oracle's float64 gradients, and the sharded (rs_ag) update path against the flat one.
+The two op-level tests also hold the reference's own rules, rmsprop and adam (ghm_rmsprop / ghm_adam in
+csrc/elementwise.hip, the oracle's rmsprop_step / adam_step in float64), to the same protocol and the same bounds."""
 import sys
 
 import numpy as np
 import pytest
 
+from oracle import ops as O
 from oracle import step as ostep
 
 pytestmark = pytest.mark.gpu
 
 NEW = ['sgd', 'momentum', 'nesterov_momentum', 'adagrad', 'adadelta', 'adamax', 'amsgrad']
-NSTATE = {'sgd': 0, 'momentum': 1, 'nesterov_momentum': 1, 'adagrad': 1, 'adadelta': 2, 'adamax': 2, 'amsgrad': 3}
-TICKS = {'adamax', 'amsgrad'}
+OLD = ['rmsprop', 'adam']          # entry points of their own: update() below is the adapter
+NSTATE = {'rmsprop': 1, 'adam': 2, 'sgd': 0, 'momentum': 1, 'nesterov_momentum': 1, 'adagrad': 1, 'adadelta': 2, 'adamax': 2, 'amsgrad': 3}
+TICKS = {'adamax', 'amsgrad', 'adam'}
 # non-default constants at op level (a swapped h0 / h1 shows), in the launch order of include/ghm.h
-CONSTS = {'sgd': (), 'momentum': (0.85,), 'nesterov_momentum': (0.85,), 'adagrad': (1e-5,), 'adadelta': (0.9, 1e-5),
+CONSTS = {'rmsprop': (0.85, 1e-5), 'adam': (0.8, 0.99, 1e-7), 'sgd': (), 'momentum': (0.85,), 'nesterov_momentum': (0.85,), 'adagrad': (1e-5,), 'adadelta': (0.9, 1e-5),
           'adamax': (0.8, 0.99, 1e-7), 'amsgrad': (0.8, 0.99, 1e-7)}
 HP_NAMES = {'sgd': (), 'momentum': ('momentum',), 'nesterov_momentum': ('momentum',), 'adagrad': ('epsilon',),
             'adadelta': ('rho', 'epsilon'), 'adamax': ('beta1', 'beta2', 'epsilon'), 'amsgrad': ('beta1', 'beta2', 'epsilon')}
@@ -25,6 +29,12 @@ def rule_ref(kind, p, g, s, lr, t, h):
     -> (p', [s'])"""
     if kind == 'sgd':
         return p - lr * g, []
+    if kind == 'rmsprop':
+        p2, a2 = O.rmsprop_step(p, g, s[0], lr, *h)
+        return p2, [a2]
+    if kind == 'adam':
+        p2, m2, v2, _ = O.adam_step(p, g, s[0], s[1], t - 1, lr, *h)
+        return p2, [m2, v2]
     if kind == 'momentum':
         (mu,) = h
         v = mu * s[0] - lr * g
@@ -80,11 +90,29 @@ def dev():
 
 # ---- op level ---------------------------------------------------------------------------------------------------------
 
+def update(ops, kind, p, g, states, n, hyper, h, grad_scale):
+    """one launch of the rule: ghm_opt_update for the seven, the reference rules' own entry points for rmsprop and adam"""
+    if kind == 'rmsprop':
+        return ops.rmsprop(p, g, states[0], n, hyper, h[0], h[1], grad_scale)
+    if kind == 'adam':
+        return ops.adam(p, g, states[0], states[1], n, hyper, h[0], h[1], h[2], grad_scale)
+    ops.opt_update(kind, p, g, states, n, hyper, h, grad_scale)
+
+
 @pytest.mark.parametrize("n", [1003, 4096, 2 ** 24 + 3])
-@pytest.mark.parametrize("kind", NEW)
+@pytest.mark.parametrize("kind", NEW + OLD)
 def test_rule_against_float64_over_five_launches(dev, kind, n):
     """five launches on one buffer set, grad_scale 0.5, a new learning rate written into hyper between launches 2 and 3,
     gradients of changing magnitude (so that amsgrad's running max and adamax's infinity norm are not just the latest value)"""
+    five_launches(dev, kind, n, 0.0)
+
+
+def test_adam_from_a_large_step_count(dev):
+    """the same protocol with hyper[1] starting at 10^5: powf(b, t) of the step size at a large t"""
+    five_launches(dev, 'adam', 4099, 1e5)
+
+
+def five_launches(dev, kind, n, t0):
     from gan_heightmaps_amd.device import Ops
     ops = Ops(dev)
     rng = np.random.RandomState(n % 1000 + len(kind))
@@ -93,8 +121,8 @@ def test_rule_against_float64_over_five_launches(dev, kind, n):
     p0 = (rng.randn(n) * 0.1).astype(np.float32)
     pd, gd = dev.tensor(p0.reshape(1, n, 1, 1)), dev.zeros((1, n, 1, 1))
     sd = [dev.zeros((1, n, 1, 1)) for _ in range(NSTATE[kind])]
-    hyper = dev.tensor(np.array([lr0, 0.0], np.float32))
-    p, s, t, lr = p0.astype(np.float64), [np.zeros(n) for _ in sd], 0, lr0
+    hyper = dev.tensor(np.array([lr0, t0], np.float32))
+    p, s, t, lr = p0.astype(np.float64), [np.zeros(n) for _ in sd], t0, lr0
     for it, mag in enumerate([1.0, 0.3, 2.0, 0.05, 1.0]):
         if it == 2:
             dev.sync()
@@ -103,7 +131,7 @@ def test_rule_against_float64_over_five_launches(dev, kind, n):
             hyper.set(hv)
         g = (rng.randn(n) * mag).astype(np.float32)
         gd.set(g)
-        ops.opt_update(kind, pd, gd, sd, n, hyper, h, 0.5)
+        update(ops, kind, pd, gd, sd, n, hyper, h, 0.5)
         if kind in TICKS:
             ops.adam_tick(hyper)
         t += 1
@@ -118,10 +146,10 @@ def test_rule_against_float64_over_five_launches(dev, kind, n):
         assert np.linalg.norm(b) > 0
         assert rel(a, b) <= 1e-6, (j, rel(a, b))
         assert rel(a[tail], b[tail]) <= 1e-6, j
-    assert hyper.numpy().ravel()[1] == (5.0 if kind in TICKS else 0.0)
+    assert hyper.numpy().ravel()[1] == t0 + (5.0 if kind in TICKS else 0.0)
 
 
-@pytest.mark.parametrize("kind", NEW)
+@pytest.mark.parametrize("kind", NEW + OLD)
 def test_loss_scale_contract(dev, kind):
     """with a loss-scale state attached: the overflow flag leaves p, every state buffer and t bit-unchanged; a clean step at
     scale S equals the unscaled launch on g / S (S a power of two: both products are exact)"""
@@ -146,13 +174,13 @@ def test_loss_scale_contract(dev, kind):
     before = snap(pd, sd, hy)
     dev.set_loss_scale_state(ls)
     try:
-        ops.opt_update(kind, pd, gd, sd, n, hy, h, 0.5)
+        update(ops, kind, pd, gd, sd, n, hy, h, 0.5)
         ops.adam_tick(hy)
         dev.sync()
         for a, b in zip(snap(pd, sd, hy), before):
             assert np.array_equal(a, b)
         ls.set(np.array([S, 1.0 / S, 0, 0, 0, 0, 0, 0], np.float32))             # clean step
-        ops.opt_update(kind, pd, gd, sd, n, hy, h, 0.5)
+        update(ops, kind, pd, gd, sd, n, hy, h, 0.5)
         if kind in TICKS:
             ops.adam_tick(hy)
         dev.sync()
@@ -160,7 +188,7 @@ def test_loss_scale_contract(dev, kind):
         dev.set_loss_scale_state(None)
     scaled = snap(pd, sd, hy)
     pd2, sd2, hy2 = dev.tensor(before[0]), [dev.tensor(x) for x in before[1:-1]], dev.tensor(before[-1])
-    ops.opt_update(kind, pd2, gd_unscaled, sd2, n, hy2, h, 0.5)
+    update(ops, kind, pd2, gd_unscaled, sd2, n, hy2, h, 0.5)
     if kind in TICKS:
         ops.adam_tick(hy2)
     dev.sync()
