@@ -19,6 +19,16 @@ class ConvDesc(C.Structure):
                 ("x_nstride", C.c_int64), ("y_nstride", C.c_int64)]
 
 
+class RenderParams(C.Structure):
+    """ghm_render_params"""
+    _fields_ = [("pos", C.c_float * 3), ("yaw", C.c_float), ("pitch", C.c_float), ("fov", C.c_float),
+                ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("height_scale", C.c_float), ("step", C.c_float), ("max_dist", C.c_float),
+                ("sun_azimuth", C.c_float), ("sun_elevation", C.c_float), ("shadows", C.c_int32),
+                ("softness", C.c_float), ("ambient", C.c_float), ("haze", C.c_float),
+                ("horizon", C.c_float * 3), ("zenith", C.c_float * 3), ("accel", C.c_int32), ("out_u8", C.c_int32)]
+
+
 _p, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _D = C.POINTER(ConvDesc)
 
@@ -167,6 +177,8 @@ SIGNATURES = {
     "ghm_world_emit": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_world_crop": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32],
     "ghm_world_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64],
+    "ghm_render_maxmip": [_p, _p, _i32, _i32, _p, _i64],
+    "ghm_render_view": [_p, C.POINTER(RenderParams), _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],
     "ghm_lsgan_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_bce_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_recon_loss": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _f, _i32],
@@ -202,7 +214,8 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_conv2d_wgrad_pooled_split_supported": ([_D], C.c_int),
             "ghm_split_pool_supported": ([_D, _i32], C.c_int),
             "ghm_split_q_direct": ([_D, _i32], C.c_int),
-            "ghm_split_dgrad_dact_supported": ([_D], C.c_int)}
+            "ghm_split_dgrad_dact_supported": ([_D], C.c_int),
+            "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)
 
 _lib = None

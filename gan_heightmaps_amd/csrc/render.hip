@@ -1,0 +1,360 @@
+// Camera views of a heightfield and its texture (gan_heightmaps_amd/render.py): a ray caster that marches every
+// image pixel's ray over the bilinear surface h = height_scale * hm on the fixed grid t_k = k * step, finds the first sample
+// at or below the surface, refines it with one secant step, and shades it (Lambert sun, soft shadow march, haze, sky).
+//   maxmip : the maximum pyramid of hm, built once per scene: texel (i, j) of level l bounds hm over every pixel a bilinear
+//            sample inside [i 2^l, (i+1) 2^l) x [j 2^l, (j+1) 2^l) can read (the square and one pixel around it);
+//   view   : one image.  With ``accel`` a ray jumps over runs of samples the pyramid proves to lie above the surface; the
+//            samples it does evaluate are the plain march's, so both give the same bits.
+// Gather-bound and latency-bound: no LDS traffic beyond a table of level offsets, no reductions, no atomics, no matrix cores.
+// A wave owns a small rectangle of neighbouring pixels, so its rays read neighbouring texels.
+#include "common.h"
+
+#include <math.h>
+
+// no fused multiply-adds: a sample's position is fl(o + fl(t d)) in the march, in the skip test and in the shading alike (the
+// skip proof needs the very same values), and the uint8 map rounds as csrc/world.hip's does
+#pragma clang fp contract(off)
+
+#define REN_MAX_LEVELS 32
+#define REN_MAX_STEPS (1 << 20)
+// what the computed bilinear value of hm (values in [0, 1]) can exceed the largest of its four pixels by stays below 2^-22
+// (three lerps of three roundings each); the bound of a skip adds 2^-18
+#define REN_MARGIN 3.814697265625e-06f
+
+namespace {
+
+struct RView {
+    float o[3];                 // camera (y, x, z), scene-local
+    float F[3], R[3], U[3];     // f * forward, right, up
+    float sun[3];
+    float horizon[3], zenith[3];
+    float hs, step, max_dist, softness, ambient, haze;
+    int H, W, Hi, Wi, K;        // K: the last sample index, floor(max_dist / step)
+    int top;                    // the pyramid's last level (1 x 1)
+    int shadows, accel, out_u8;
+    uint32_t off[REN_MAX_LEVELS];
+};
+
+__host__ __device__ inline int ren_levels(int H, int W) {
+    int top = 0;
+    while (((H + (1 << top) - 1) >> top) > 1 || ((W + (1 << top) - 1) >> top) > 1) ++top;
+    return top;
+}
+
+// elements of the pyramid of an H x W map, and (off != null) the offset of every level
+inline int64_t ren_layout(int H, int W, uint32_t* off) {
+    const int top = ren_levels(H, W);
+    int64_t n = 0;
+    for (int l = 0; l <= top; ++l) {
+        if (off) off[l] = (uint32_t)n;
+        n += (int64_t)((H + (1 << l) - 1) >> l) * ((W + (1 << l) - 1) >> l);
+    }
+    return n;
+}
+
+// level 0: the 3 x 3 maximum around every pixel, clamped at the border
+__global__ __launch_bounds__(256) void ren_mip0_kernel(const float* __restrict__ hm, int H, int W, float* __restrict__ out) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)H * W) return;
+    const int i = (int)(idx / W), j = (int)(idx - (long)i * W);
+    const int i0 = max(i - 1, 0), i1 = min(i + 1, H - 1), j0 = max(j - 1, 0), j1 = min(j + 1, W - 1);
+    float m = hm[(long)i * W + j];
+    for (int a = i0; a <= i1; ++a)
+        for (int b = j0; b <= j1; ++b) m = fmaxf(m, hm[(long)a * W + b]);
+    out[idx] = m;
+}
+
+// level l from level l - 1: the maximum of the 2 x 2 children (the children's aprons make up the parent's)
+__global__ __launch_bounds__(256) void ren_mip_kernel(const float* __restrict__ src, int sh, int sw, float* __restrict__ dst,
+                                                      int dh, int dw) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)dh * dw) return;
+    const int i = (int)(idx / dw), j = (int)(idx - (long)i * dw);
+    const int a0 = 2 * i, a1 = min(2 * i + 1, sh - 1), b0 = 2 * j, b1 = min(2 * j + 1, sw - 1);
+    dst[idx] = fmaxf(fmaxf(src[(long)a0 * sw + b0], src[(long)a0 * sw + b1]),
+                     fmaxf(src[(long)a1 * sw + b0], src[(long)a1 * sw + b1]));
+}
+
+// bilinear sample of one plane at (y, x): the position moves by -0.5 and is clamped to the pixel centres
+__device__ __forceinline__ float ren_bil(const float* __restrict__ p, int H, int W, float y, float x) {
+    const float fy = fminf(fmaxf(y - 0.5f, 0.0f), (float)(H - 1));
+    const float fx = fminf(fmaxf(x - 0.5f, 0.0f), (float)(W - 1));
+    const int i0 = (int)fy, j0 = (int)fx;
+    const int i1 = min(i0 + 1, H - 1), j1 = min(j0 + 1, W - 1);
+    const float wy = fy - (float)i0, wx = fx - (float)j0;
+    const float a = p[(long)i0 * W + j0], b = p[(long)i0 * W + j1];
+    const float c = p[(long)i1 * W + j0], d = p[(long)i1 * W + j1];
+    const float t = a + wx * (b - a);
+    const float u = c + wx * (d - c);
+    return t + wy * (u - t);
+}
+
+struct RRay {
+    float oy, ox, oz, dy, dx, dz;
+};
+
+__device__ __forceinline__ void ren_pos(const RRay& r, float step, int k, float& y, float& x, float& z) {
+    const float t = (float)k * step;
+    y = r.oy + t * r.dy;
+    x = r.ox + t * r.dx;
+    z = r.oz + t * r.dz;
+}
+
+// g_k: the height of sample k above the surface, +inf outside the scene's rectangle
+__device__ __forceinline__ float ren_gap(const RView& v, const float* __restrict__ hm, const RRay& r, int k) {
+    float y, x, z;
+    ren_pos(r, v.step, k, y, x, z);
+    if (!(y >= 0.0f && y <= (float)v.H && x >= 0.0f && x <= (float)v.W)) return INFINITY;
+    return z - v.hs * ren_bil(hm, v.H, v.W, y, x);
+}
+
+// true if every sample k .. k + n - 1 (n >= 2) is proven to have g > 0.  The samples' coordinates are monotone in the index
+// (fl(j step), fl(t d) and fl(o + .) are monotone maps), so the two end samples -- computed as the march computes them --
+// bound the run's box and its lowest z; the box spans less than 2^l per axis, so at most 2 x 2 texels of level l cover it.
+__device__ __forceinline__ bool ren_skip(const RView& v, const float* __restrict__ mip, const uint32_t* s_off, const RRay& r,
+                                         int k, int n) {
+    float ya, xa, za, yb, xb, zb;
+    ren_pos(r, v.step, k, ya, xa, za);
+    ren_pos(r, v.step, k + n - 1, yb, xb, zb);
+    float ylo = fminf(ya, yb), yhi = fmaxf(ya, yb), xlo = fminf(xa, xb), xhi = fmaxf(xa, xb);
+    const float Hf = (float)v.H, Wf = (float)v.W;
+    if (yhi < 0.0f || ylo > Hf || xhi < 0.0f || xlo > Wf) return true;       // the whole run is outside: g = +inf
+    ylo = fmaxf(ylo, 0.0f);
+    xlo = fmaxf(xlo, 0.0f);
+    yhi = fminf(yhi, Hf);
+    xhi = fminf(xhi, Wf);
+    const int span = (int)fmaxf(yhi - ylo, xhi - xlo);                        // floor; 2^l > span below
+    const int l = min(32 - __clz(span), v.top);
+    const int ny = (v.H + (1 << l) - 1) >> l, nx = (v.W + (1 << l) - 1) >> l;
+    const int iy0 = min((int)ylo >> l, ny - 1), iy1 = min((int)yhi >> l, ny - 1);
+    const int ix0 = min((int)xlo >> l, nx - 1), ix1 = min((int)xhi >> l, nx - 1);
+    if (iy1 - iy0 > 1 || ix1 - ix0 > 1) return false;
+    const float* lv = mip + s_off[l];
+    const float m = fmaxf(fmaxf(lv[(long)iy0 * nx + ix0], lv[(long)iy0 * nx + ix1]),
+                          fmaxf(lv[(long)iy1 * nx + ix0], lv[(long)iy1 * nx + ix1]));
+    return fminf(za, zb) > v.hs * (m + REN_MARGIN);
+}
+
+template <int TW, int TH>
+__global__ __launch_bounds__(256) void ren_view_kernel(const RView v, const float* __restrict__ hm,
+                                                       const float* __restrict__ tex, const float* __restrict__ mip,
+                                                       void* __restrict__ out, float* __restrict__ depth) {
+    __shared__ uint32_t s_off[REN_MAX_LEVELS];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < REN_MAX_LEVELS; ++i) s_off[i] = v.off[i];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pu = (blockIdx.x * 2 + (wave & 1)) * TW + lane % TW;
+    const int pv = (blockIdx.y * 2 + (wave >> 1)) * TH + lane / TW;
+    if (pu >= v.Wi || pv >= v.Hi) return;
+
+    const float a = ((float)pu + 0.5f) - 0.5f * (float)v.Wi;
+    const float b = ((float)pv + 0.5f) - 0.5f * (float)v.Hi;
+    RRay r;
+    r.oy = v.o[0];
+    r.ox = v.o[1];
+    r.oz = v.o[2];
+    {
+        const float dy = v.F[0] + a * v.R[0] - b * v.U[0];
+        const float dx = v.F[1] + a * v.R[1] - b * v.U[1];
+        const float dz = v.F[2] + a * v.R[2] - b * v.U[2];
+        const float len = sqrtf(dy * dy + dx * dx + dz * dz);
+        r.dy = dy / len;
+        r.dx = dx / len;
+        r.dz = dz / len;
+    }
+    const float sky_w = fmaxf(r.dz, 0.0f);
+    float col[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) col[c] = v.horizon[c] + sky_w * (v.zenith[c] - v.horizon[c]);
+    float t_hit = INFINITY;
+
+    // ---- the march: the first k in [0, K] with g_k <= 0 ----
+    // n: the length of the run to try next (1: evaluate a sample; always 1 in the plain march), cap: its limit -- twice
+    // what last succeeded or failed, so a ray close to the ground wastes at most two tries per sample
+    int k = 0, kprev = -1, n = 1, cap = REN_MAX_STEPS;
+    float g = INFINITY, gprev = INFINITY;
+    bool hit = false;
+    while (k <= v.K) {
+        if (n >= 2) {
+            const int ne = min(n, v.K - k + 1);
+            if (ne >= 2 && ren_skip(v, mip, s_off, r, k, ne)) {
+                k += ne;
+                n = cap = min(2 * ne, REN_MAX_STEPS);
+                continue;
+            }
+            n = ne >> 1;
+            cap = max(2 * n, 4);
+            if (n >= 2) continue;
+        }
+        g = ren_gap(v, hm, r, k);
+        if (g <= 0.0f) {
+            hit = true;
+            break;
+        }
+        gprev = g;
+        kprev = k;
+        ++k;
+        // the clearance in steps is how far a skip is worth trying (a heuristic: it changes the cost, never the result)
+        if (v.accel) n = min((int)fminf(g / v.step, (float)REN_MAX_STEPS), cap);
+    }
+
+    if (hit) {
+        t_hit = (float)k * v.step;
+        if (k > 0) {
+            if (kprev != k - 1) gprev = ren_gap(v, hm, r, k - 1);       // skipped: the plain march's value, computed now
+            if (gprev < INFINITY) t_hit = (float)(k - 1) * v.step + v.step * gprev / (gprev - g);
+        }
+        const float qy = r.oy + t_hit * r.dy, qx = r.ox + t_hit * r.dx, qz = r.oz + t_hit * r.dz;
+        const float gy = 0.5f * v.hs * (ren_bil(hm, v.H, v.W, qy + 1.0f, qx) - ren_bil(hm, v.H, v.W, qy - 1.0f, qx));
+        const float gx = 0.5f * v.hs * (ren_bil(hm, v.H, v.W, qy, qx + 1.0f) - ren_bil(hm, v.H, v.W, qy, qx - 1.0f));
+        const float nl = sqrtf(gy * gy + gx * gx + 1.0f);
+        const float ndots = (-gy * v.sun[0] - gx * v.sun[1] + v.sun[2]) / nl;
+        float shadow = 1.0f;
+        if (v.shadows && ndots > 0.0f) {
+            float lo = INFINITY;
+            for (int m = 1; m <= v.K; ++m) {
+                const float t = (float)m * v.step;
+                const float y = qy + t * v.sun[0], x = qx + t * v.sun[1], z = qz + t * v.sun[2];
+                if (!(y >= 0.0f && y <= (float)v.H && x >= 0.0f && x <= (float)v.W) || z > v.hs) break;
+                lo = fminf(lo, (z - v.hs * ren_bil(hm, v.H, v.W, y, x)) / t);
+                if (lo <= 0.0f) break;                                   // the clamp below makes it 0 whatever follows
+            }
+            if (lo < INFINITY) shadow = fminf(fmaxf(v.softness * lo, 0.0f), 1.0f);
+        }
+        const float shade = v.ambient + (1.0f - v.ambient) * fmaxf(ndots, 0.0f) * shadow;
+        const float fog = 1.0f - expf(-v.haze * t_hit);
+        const long plane = (long)v.H * v.W;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float tc = ren_bil(tex + c * plane, v.H, v.W, qy, qx) * shade;
+            col[c] = tc * (1.0f - fog) + col[c] * fog;
+        }
+    }
+
+    const long pix = (long)pv * v.Wi + pu;
+    if (depth) depth[pix] = t_hit;
+    if (v.out_u8) {
+        unsigned char* o8 = (unsigned char*)out + 3 * pix;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float f = fminf(fmaxf(col[c], 0.0f), 1.0f);
+            o8[c] = (unsigned char)(int)rint((double)f * 255.0);       // half to even, as util.to_uint8
+        }
+    } else {
+        float* of = (float*)out;
+        const long img = (long)v.Hi * v.Wi;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) of[c * img + pix] = col[c];
+    }
+}
+
+inline bool fin(double x) { return std::isfinite(x); }
+
+}  // namespace
+
+extern "C" {
+
+int64_t ghm_render_maxmip_elems(int32_t H, int32_t W) {
+    if (H < 2 || W < 2 || (int64_t)H * W >= ((int64_t)1 << 31)) return -1;
+    return ren_layout(H, W, nullptr);
+}
+
+int ghm_render_maxmip(ghm_ctx* ctx, const float* hm, int32_t H, int32_t W, float* mip, int64_t mip_elems) {
+    GHM_CHECK(hm && mip, "ghm_render_maxmip: null pointer");
+    GHM_CHECK(H >= 2 && W >= 2 && (int64_t)H * W < ((int64_t)1 << 31), "ghm_render_maxmip: scene %d x %d out of range", H, W);
+    uint32_t off[REN_MAX_LEVELS] = {};
+    const int64_t need = ren_layout(H, W, off);
+    GHM_CHECK(mip_elems == need, "ghm_render_maxmip: the pyramid of %d x %d holds %lld elements, the buffer %lld", H, W,
+              (long long)need, (long long)mip_elems);
+    const int top = ren_levels(H, W);
+    hipLaunchKernelGGL(ren_mip0_kernel, EW_GRID((long)H * W), hm, H, W, mip);
+    for (int l = 1; l <= top; ++l) {
+        const int sh = (H + (1 << (l - 1)) - 1) >> (l - 1), sw = (W + (1 << (l - 1)) - 1) >> (l - 1);
+        const int dh = (H + (1 << l) - 1) >> l, dw = (W + (1 << l) - 1) >> l;
+        const float* src = mip + off[l - 1];
+        float* dst = mip + off[l];
+        hipLaunchKernelGGL(ren_mip_kernel, EW_GRID((long)dh * dw), src, sh, sw, dst, dh, dw);
+    }
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+int ghm_render_view(ghm_ctx* ctx, const ghm_render_params* p, const float* hm, const float* tex, int32_t H, int32_t W,
+                    const float* mip, int32_t mip_H, int32_t mip_W, void* out, float* depth) {
+    GHM_CHECK(p && hm && tex && out, "ghm_render_view: null pointer");
+    GHM_CHECK(H >= 2 && W >= 2 && (int64_t)H * W < ((int64_t)1 << 31), "ghm_render_view: scene %d x %d out of range", H, W);
+    GHM_CHECK(p->Hi >= 1 && p->Wi >= 1 && (int64_t)p->Hi * p->Wi < ((int64_t)1 << 31),
+              "ghm_render_view: image %d x %d out of range", p->Hi, p->Wi);
+    GHM_CHECK(fin(p->step) && fin(p->max_dist) && p->step > 0.0f && p->max_dist > 0.0f,
+              "ghm_render_view: step=%g max_dist=%g must be positive", (double)p->step, (double)p->max_dist);
+    GHM_CHECK(fin(p->fov) && p->fov > 0.0f && (double)p->fov < M_PI, "ghm_render_view: fov=%g outside (0, pi)", (double)p->fov);
+    GHM_CHECK(fin(p->pos[0]) && fin(p->pos[1]) && fin(p->pos[2]) && fin(p->yaw) && fin(p->pitch),
+              "ghm_render_view: the camera has a non-finite field");
+    GHM_CHECK(fin(p->height_scale) && p->height_scale > 0.0f && fin(p->sun_azimuth) && fin(p->sun_elevation) &&
+                  fin(p->softness) && p->softness >= 0.0f && fin(p->ambient) && fin(p->haze) && p->haze >= 0.0f,
+              "ghm_render_view: bad light or scale (height_scale=%g haze=%g)", (double)p->height_scale, (double)p->haze);
+    for (int c = 0; c < 3; ++c)
+        GHM_CHECK(fin(p->horizon[c]) && fin(p->zenith[c]), "ghm_render_view: non-finite sky colour");
+    // the marching loops end at this count and at nothing else
+    const double steps = floor((double)p->max_dist / (double)p->step);
+    GHM_CHECK(steps <= (double)REN_MAX_STEPS, "ghm_render_view: max_dist / step = %g samples per ray, at most %d", steps,
+              REN_MAX_STEPS);
+    if (p->accel) {
+        GHM_CHECK(mip, "ghm_render_view: accel needs the pyramid");
+        GHM_CHECK(mip_H == H && mip_W == W, "ghm_render_view: the pyramid was built for %d x %d, the scene is %d x %d", mip_H,
+                  mip_W, H, W);
+    }
+    RView v = {};
+    const double cy = cos((double)p->yaw), sy = sin((double)p->yaw), cp = cos((double)p->pitch), sp = sin((double)p->pitch);
+    const double f = 0.5 * p->Hi / tan(0.5 * (double)p->fov);
+    const double fw[3] = {cp * cy, cp * sy, sp}, rt[3] = {sy, -cy, 0.0}, up[3] = {-sp * cy, -sp * sy, cp};
+    const double ce = cos((double)p->sun_elevation), se = sin((double)p->sun_elevation);
+    const double sun[3] = {ce * cos((double)p->sun_azimuth), ce * sin((double)p->sun_azimuth), se};
+    for (int c = 0; c < 3; ++c) {
+        v.o[c] = p->pos[c];
+        v.F[c] = (float)(f * fw[c]);
+        v.R[c] = (float)rt[c];
+        v.U[c] = (float)up[c];
+        v.sun[c] = (float)sun[c];
+        v.horizon[c] = p->horizon[c];
+        v.zenith[c] = p->zenith[c];
+    }
+    GHM_CHECK(fin(v.F[0]) && fin(v.F[1]) && fin(v.F[2]), "ghm_render_view: fov=%g gives no finite focal length", (double)p->fov);
+    v.hs = p->height_scale;
+    v.step = p->step;
+    v.max_dist = p->max_dist;
+    v.softness = p->softness;
+    v.ambient = p->ambient;
+    v.haze = p->haze;
+    v.H = H;
+    v.W = W;
+    v.Hi = p->Hi;
+    v.Wi = p->Wi;
+    v.K = (int)steps;
+    v.top = ren_levels(H, W);
+    v.shadows = p->shadows ? 1 : 0;
+    v.accel = p->accel ? 1 : 0;
+    v.out_u8 = p->out_u8 ? 1 : 0;
+    ren_layout(H, W, v.off);
+    // TUNING: GHM_RENDER_TILE=16x4 | 4x16 | 8x8 -- the rectangle of pixels one wave owns
+    const char* tile = GHM_OPT("GHM_RENDER_TILE");
+    const std::string ts = tile ? tile : "8x8";
+    if (ts == "16x4") {
+        hipLaunchKernelGGL((ren_view_kernel<16, 4>), dim3(ceil_div(v.Wi, 32), ceil_div(v.Hi, 8)), dim3(256), 0, ctx->stream, v,
+                           hm, tex, mip, out, depth);
+    } else if (ts == "4x16") {
+        hipLaunchKernelGGL((ren_view_kernel<4, 16>), dim3(ceil_div(v.Wi, 8), ceil_div(v.Hi, 32)), dim3(256), 0, ctx->stream, v,
+                           hm, tex, mip, out, depth);
+    } else {
+        GHM_CHECK(ts == "8x8", "ghm_render_view: GHM_RENDER_TILE=%s (8x8, 16x4 or 4x16)", ts.c_str());
+        hipLaunchKernelGGL((ren_view_kernel<8, 8>), dim3(ceil_div(v.Wi, 16), ceil_div(v.Hi, 16)), dim3(256), 0, ctx->stream, v,
+                           hm, tex, mip, out, depth);
+    }
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -396,6 +396,30 @@ class WorldTile(C.Structure):
     _fields_ = [("chunk", C.c_void_p * 4), ("y0", C.c_int32), ("x0", C.c_int32)]
 
 
+class MaxMip:
+    """the maximum pyramid of one scene (Ops.render_maxmip): the device buffer and the size it was built for"""
+    __slots__ = ("ptr", "H", "W", "elems")
+
+    def __init__(self, ptr, H, W, elems):
+        self.ptr, self.H, self.W, self.elems = ptr, H, W, elems
+
+
+def render_params(pos, yaw, pitch, fov, size, height_scale, step, max_dist, sun_azimuth, sun_elevation, shadows, softness,
+                  ambient, haze, horizon, zenith, accel=True, out_u8=False):
+    """a ghm_render_params (include/ghm.h); pos is the scene-local (y, x, z)"""
+    p = _lib.RenderParams()
+    p.pos[:] = [float(v) for v in pos]
+    p.yaw, p.pitch, p.fov = float(yaw), float(pitch), float(fov)
+    p.Hi, p.Wi = int(size[0]), int(size[1])
+    p.height_scale, p.step, p.max_dist = float(height_scale), float(step), float(max_dist)
+    p.sun_azimuth, p.sun_elevation = float(sun_azimuth), float(sun_elevation)
+    p.shadows, p.softness, p.ambient, p.haze = int(bool(shadows)), float(softness), float(ambient), float(haze)
+    p.horizon[:] = [float(v) for v in horizon]
+    p.zenith[:] = [float(v) for v in zenith]
+    p.accel, p.out_u8 = int(bool(accel)), int(bool(out_u8))
+    return p
+
+
 def _vp(x):
     if x is None:
         return C.c_void_p(0)
@@ -1063,6 +1087,29 @@ class Ops:
             t.y0, t.x0 = y0, x0
         assert dst.H == dst.W
         call("ghm_world_gather", self.h, tab, len(tiles), dst.N, dst.Cc, dst.H, K, _vp(dst), dst.nstride)
+
+    # camera views of a heightfield (csrc/render.hip, gan_heightmaps_amd/render.py)
+    def render_maxmip(self, hm_ptr, H, W):
+        """the maximum pyramid of the fp32 [H, W] map at hm_ptr -> a MaxMip (a new device buffer; free it with
+        dev.free(mip.ptr))"""
+        n = _lib.load().ghm_render_maxmip_elems(int(H), int(W))
+        if n < 0:
+            raise _lib.GhmError("ghm_render_maxmip_elems: scene %d x %d out of range" % (H, W))
+        ptr = self.dev.alloc(4 * n)
+        try:
+            call("ghm_render_maxmip", self.h, C.c_void_p(int(hm_ptr)), int(H), int(W), C.c_void_p(ptr), n)
+        except Exception:
+            self.dev.free(ptr)
+            raise
+        return MaxMip(ptr, int(H), int(W), n)
+
+    def render_view(self, params, hm_ptr, tex_ptr, H, W, mip, out_ptr, depth_ptr=None):
+        """one image of the scene (hm fp32 [H, W], tex fp32 [3, H, W]) -> out_ptr: fp32 [3, Hi, Wi], or uint8 [Hi, Wi, 3]
+        with params.out_u8; depth_ptr (optional): fp32 [Hi, Wi], t_hit or +inf.  params: a RenderParams (render_params());
+        mip: the scene's MaxMip, or None with params.accel = 0"""
+        call("ghm_render_view", self.h, C.byref(params) if params is not None else None, _vp(hm_ptr), _vp(tex_ptr), int(H),
+             int(W), _vp(mip.ptr if mip is not None else None), mip.H if mip is not None else 0,
+             mip.W if mip is not None else 0, _vp(out_ptr), _vp(depth_ptr))
 
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous

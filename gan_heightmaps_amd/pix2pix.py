@@ -159,6 +159,17 @@ class Pix2Pix:
         from .world import TerrainWorld
         return TerrainWorld(self, seed, **kw)
 
+    def render_terrain(self, heightmap, texture, camera, height_scale=None, **kw):
+        """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
+        ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in
+        the heightmap's pixel coordinates; kw: Scene.render's (sun, shadows, haze, step, max_dist, uint8, out, accel).
+        For many frames of one terrain build a render.Scene once instead.  Leaves the training state untouched."""
+        from .render import DEFAULTS, Scene
+        self.engine.sync()
+        with Scene(heightmap, texture, height_scale=DEFAULTS['height_scale'] if height_scale is None else height_scale,
+                   value_range=(self.is_a_grayscale, self.is_b_grayscale), device=self.device) as scene:
+            return scene.render(camera, **kw)
+
     def _is_writer(self):
         """files (results.txt, PNG dumps, checkpoints) are written by rank 0 only; every rank still runs the
         forward passes and iterator draws of the per-epoch dumps, which are part of the training trajectory"""

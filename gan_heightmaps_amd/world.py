@@ -348,6 +348,21 @@ class TerrainWorld:
         """(heightmap, texture) of one rectangle from one pass over the chunks; bit for bit the two separate calls"""
         return self._request(y0, x0, h, w, True, True, out_heightmap, out_texture, uint8, uint8)
 
+    def scene(self, y0, x0, h, w, **kw):
+        """the rectangle as a render.Scene with origin (y0, x0): ``both`` in float32, uploaded once.  Cameras are
+        given in world coordinates.  kw: height_scale.  Close it, or use it as a context manager."""
+        from .render import Scene
+        hm, tex = self.both(y0, x0, h, w)
+        return Scene(hm, tex, origin=(y0, x0), value_range=(self.model.is_a_grayscale, self.model.is_b_grayscale),
+                     device=self.model.device, **kw)
+
+    def view(self, camera, max_dist, height_scale=None, **kw):
+        """one image of the world from ``camera`` (world coordinates, negative ones included), rays ``max_dist`` long: the
+        scene of camera.footprint(max_dist), rendered.  kw: Scene.render's."""
+        skw = {} if height_scale is None else {"height_scale": height_scale}
+        with self.scene(*camera.footprint(max_dist), **skw) as scene:
+            return scene.render(camera, max_dist=max_dist, **kw)
+
     def _request(self, y0, x0, h, w, want_hm, want_tex, out_hm, out_tex, hm_u8, tex_u8):
         from .device import PinnedArray
         y0, x0, h, w = self._check_region(y0, x0, h, w)
