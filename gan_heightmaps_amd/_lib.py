@@ -171,11 +171,14 @@ SIGNATURES = {
     "ghm_texture_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_texture_blend": [_p, _p, _i32, _i32, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "ghm_texture_finalize": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "ghm_texture_finalize_scene": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32,
+                                   _p],
     "ghm_terrain_seed": [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_terrain_emit": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_world_seed": [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_world_emit": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_world_crop": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32],
+    "ghm_world_scene_height": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _p],
     "ghm_world_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_render_maxmip": [_p, _p, _i32, _i32, _p, _i64],
     "ghm_render_view": [_p, C.POINTER(RenderParams), _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],

@@ -1,12 +1,14 @@
 // Tiled inference over heightmaps of any size (gan_heightmaps_amd/texture.py): the canvas is cut into
 // in_shp x in_shp tiles that overlap by ``o`` pixels, every tile goes through the U-Net's forward plan, and the overlaps are
-// cross-faded with separable linear ramps.  Three HBM-bound streaming kernels around the forward pass:
+// cross-faded with separable linear ramps.  Four HBM-bound streaming kernels around the forward pass:
 //   gather   : a band of input rows (uint8 NHWC or normalised fp32 CHW) -> the plan's fp32 NCHW input view, with the
 //              half-sample-symmetric 'reflect' rule of ghm_image_batch at all four canvas borders;
 //   blend    : acc += w * u for the tiles of one forward batch, gather form (a thread owns its accumulator pixels and walks
 //              the batch's tiles in order: no atomics, bit-repeatable);
 //   finalize : acc / sum(w) of rows no later tile row touches, as fp32 CHW or as the uint8 HWC RGB of
-//              util.to_uint8(util.convert_to_rgb(.)).  sum(w) is recomputed from the plan (no weight buffer).
+//              util.to_uint8(util.convert_to_rgb(.)).  sum(w) is recomputed from the plan (no weight buffer);
+//   scene    : the same fp32 values mapped to [0, 1] and written into the three texture planes of a render scene on the
+//              device.
 // No LDS, no reductions.  Lanes run along the canvas columns, 4 per thread where the row geometry allows 16-byte accesses.
 #include "common.h"
 
@@ -45,6 +47,20 @@ __device__ __forceinline__ void tex_cover(int y, int n, int pad, int T, int o, f
     const int lo = two ? hi - 1 : hi;
     w0 = tex_w(lo, y + pad - lo * s, n, T, o);
     w1 = two ? tex_w(hi, y + pad - hi * s, n, T, o) : 0.0f;
+}
+
+// sum(w) at canvas column x of a row whose covering tile rows weigh wy0, wy1: the blend's order, tile rows, then tile
+// columns (a missing second tile adds an exact 0)
+__device__ __forceinline__ float tex_sum_w(float wy0, float wy1, int x, int nx, int pad_x, int T, int o) {
+    float wx0, wx1;
+    tex_cover(x, nx, pad_x, T, o, wx0, wx1);
+    float z = mul_rn(wy0, wx0);
+    if (wx1 != 0.0f) z = add_rn(z, mul_rn(wy0, wx1));
+    if (wy1 != 0.0f) {
+        z = add_rn(z, mul_rn(wy1, wx0));
+        if (wx1 != 0.0f) z = add_rn(z, mul_rn(wy1, wx1));
+    }
+    return z;
 }
 
 template <int VEC>
@@ -139,18 +155,7 @@ __global__ __launch_bounds__(256) void tex_finalize_kernel(const float* __restri
     tex_cover(yc0 + r0 + r, ny, pad_y, T, o, wy0, wy1);
     float sw[VEC];
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        float wx0, wx1;
-        tex_cover(x0 + k, nx, pad_x, T, o, wx0, wx1);
-        // the blend's order: tile rows, then tile columns (a missing second tile adds an exact 0)
-        float z = mul_rn(wy0, wx0);
-        if (wx1 != 0.0f) z = add_rn(z, mul_rn(wy0, wx1));
-        if (wy1 != 0.0f) {
-            z = add_rn(z, mul_rn(wy1, wx0));
-            if (wx1 != 0.0f) z = add_rn(z, mul_rn(wy1, wx1));
-        }
-        sw[k] = z;
-    }
+    for (int k = 0; k < VEC; ++k) sw[k] = tex_sum_w(wy0, wy1, x0 + k, nx, pad_x, T, o);
     float v[3][VEC];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -203,6 +208,59 @@ __global__ __launch_bounds__(256) void tex_finalize_kernel(const float* __restri
         op[1] = px[1];
         op[2] = px[2];
     }
+}
+
+// tex_finalize_kernel's fp32 values, written where a render scene keeps its texture: accumulator rows
+// [r0, r0 + nrows) (canvas rows yc0 + r0 + ...) -> rows yc0 + r0 + ... of the three unit planes out [3, H, Ws], Ws <= W
+// columns of each row.  v = acc / sum(w) by the very operations of the fp32 path above, in its order (sum(w): tile rows,
+// then tile columns; then one __fdiv_rn); then render.Scene's host map of a texture: util.convert_to_rgb in float32 -- for
+// the tanh range fl(fl(fl(v 127.5) + 127.5) / 255), three roundings kept apart by this file's `fp contract(off)` and the
+// correctly rounded __fdiv_rn -- clipped to [0, 1] (the sign of a zero is no part of the contract, csrc/world.hip), one
+// channel replicated to three planes.  A non-finite v sets *flag with a plain store.
+template <int VEC>
+__global__ __launch_bounds__(256) void tex_scene_kernel(const float* __restrict__ acc, int W, int T, int C, int r0, int nrows,
+                                                        int yc0, int ny, int pad_y, int nx, int pad_x, int o, int b_grey,
+                                                        float* __restrict__ out, int H, int Ws, int* __restrict__ flag) {
+    const int per_row = Ws / VEC;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)nrows * per_row) return;
+    const int r = (int)(idx / per_row);
+    const int x0 = (int)(idx - (long)r * per_row) * VEC;
+    float wy0, wy1;
+    tex_cover(yc0 + r0 + r, ny, pad_y, T, o, wy0, wy1);
+    float sw[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) sw[k] = tex_sum_w(wy0, wy1, x0 + k, nx, pad_x, T, o);
+    bool bad = false;
+    float* orow = out + (long)(yc0 + r0 + r) * Ws + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (c >= C) break;
+        const float* ap = acc + ((long)c * T + r0 + r) * W + x0;
+        float q[VEC];
+        if constexpr (VEC == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(ap);
+            q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
+        } else {
+            q[0] = ap[0];
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            float f = __fdiv_rn(q[k], sw[k]);
+            bad = bad || !isfinite(f);
+            if (!b_grey) f = __fdiv_rn(add_rn(mul_rn(f, 127.5f), 127.5f), 255.0f);
+            f = f > 0.0f ? f : 0.0f;
+            q[k] = f < 1.0f ? f : 1.0f;
+        }
+        for (int p = c; p < (C == 1 ? 3 : c + 1); ++p) {
+            float* op = orow + (long)p * H * Ws;
+            if constexpr (VEC == 4)
+                *reinterpret_cast<float4*>(op) = make_float4(q[0], q[1], q[2], q[3]);
+            else
+                op[0] = q[0];
+        }
+    }
+    if (bad) *flag = 1;
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -271,6 +329,30 @@ int ghm_texture_finalize(ghm_ctx* ctx, const float* acc, int32_t W, int32_t T, i
     } else {
         hipLaunchKernelGGL(tex_finalize_kernel<1>, EW_GRID((long)nrows * W), acc, W, T, C, r0, nrows, yc0, ny, pad_y, nx,
                            pad_x, overlap, out_u8 ? 1 : 0, b_grey ? 1 : 0, out);
+    }
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+int ghm_texture_finalize_scene(ghm_ctx* ctx, const float* acc, int32_t W, int32_t T, int32_t C, int32_t r0, int32_t nrows,
+                               int32_t yc0, int32_t ny, int32_t pad_y, int32_t nx, int32_t pad_x, int32_t overlap,
+                               int32_t b_grey, float* out, int32_t H, int32_t Ws, int32_t* flag) {
+    if (tex_check_axis(W, T, overlap)) return -2;
+    GHM_CHECK(acc && out && flag && (C == 1 || C == 3), "ghm_texture_finalize_scene: bad arguments (C=%d)", C);
+    GHM_CHECK(r0 >= 0 && nrows >= 0 && r0 + nrows <= T, "ghm_texture_finalize_scene: rows [%d, %d) outside the band of %d", r0,
+              r0 + nrows, T);
+    GHM_CHECK(H >= 1 && Ws >= 1 && Ws <= W && (int64_t)H * Ws < ((int64_t)1 << 31),
+              "ghm_texture_finalize_scene: a scene of %d x %d from an accumulator %d wide", H, Ws, W);
+    GHM_CHECK((int64_t)yc0 + r0 >= 0 && (int64_t)yc0 + r0 + nrows <= H,
+              "ghm_texture_finalize_scene: rows [%d, %d) outside the scene of %d", yc0 + r0, yc0 + r0 + nrows, H);
+    if (nrows == 0) return 0;
+    // Ws % 4 == 0 puts every row of every plane on a 16-byte boundary (a flight's windows are snapped to such widths)
+    if (W % 4 == 0 && Ws % 4 == 0 && al16(acc) && al16(out)) {
+        hipLaunchKernelGGL(tex_scene_kernel<4>, EW_GRID((long)nrows * (Ws / 4)), acc, W, T, C, r0, nrows, yc0, ny, pad_y, nx,
+                           pad_x, overlap, b_grey ? 1 : 0, out, H, Ws, flag);
+    } else {
+        hipLaunchKernelGGL(tex_scene_kernel<1>, EW_GRID((long)nrows * Ws), acc, W, T, C, r0, nrows, yc0, ny, pad_y, nx, pad_x,
+                           overlap, b_grey ? 1 : 0, out, H, Ws, flag);
     }
     GHM_LAUNCH_CHECK();
     return 0;

@@ -1,11 +1,13 @@
 // Regions of an unbounded seeded world, chunk by chunk (gan_heightmaps_amd/world.py): the seed canvas of
-// terrain.hip without borders, cut into square chunks that are anchored to world coordinates.  Four HBM-bound streaming
+// terrain.hip without borders, cut into square chunks that are anchored to world coordinates.  Five HBM-bound streaming
 // kernels around the trunk's and the U-Net's forward passes:
 //   seed   : a rows x cols rectangle of the unbounded seed canvas at any integer origin -> fp32 [C, rows, cols] at the trunk
 //            plan's input view, from a table of the head maps of the cell block the rectangle reads;
 //   emit   : the centre K x K of the trunk's output -> a resident fp32 chunk buffer [C, K, K];
 //   crop   : a sub-rectangle of a chunk buffer -> a staging buffer with a row pitch, as fp32 CHW or as the uint8 map of
 //            util.to_uint8(util.convert_to_rgb(.));
+//   scene  : a sub-rectangle of a chunk buffer -> the height plane of a render scene on the device, mapped to
+//            [0, 1] as render.Scene maps it on the host, bit for bit;
 //   gather : a batch of U-Net input tiles, each from the at most four chunk buffers it straddles -> the forward plan's input.
 // No LDS, no reductions, no atomics.  Lanes run along the columns, 4 per thread where the geometry allows 16-byte accesses.
 #include "common.h"
@@ -174,6 +176,60 @@ __global__ __launch_bounds__(256) void wld_crop_kernel(const float* __restrict__
     }
 }
 
+// util.convert_to_rgb's map of one value to [0, 1] as numpy evaluates it in float32: the tanh range by three separately
+// rounded operations (the product and the sum stay apart under this file's `fp contract(off)`; __fdiv_rn is the correctly
+// rounded IEEE quotient whatever the division flags of the build), then the clip to [0, 1].  The sign of a zero is no part
+// of the contract: numpy's own clip loops disagree on what becomes of -0, and -0 == +0 wherever the renderer compares
+__device__ __forceinline__ float wld_unit(float f, int grey) {
+    if (!grey) f = __fdiv_rn(add_rn(mul_rn(f, 127.5f), 127.5f), 255.0f);
+    f = f > 0.0f ? f : 0.0f;
+    return f < 1.0f ? f : 1.0f;
+}
+
+// rows [r0, r0 + nr) x columns [c0, c0 + nc) of chunk [C, K, K] -> the scene's height plane dst [H, W] at (y, x), as
+// render.Scene maps a heightmap on the host: wld_unit per channel, and for C == 3 the mean of the three mapped channels as
+// hm.astype(float64).mean(0).astype(float32) computes it -- ((a + b) + c) / 3 in double (the language's `/` on doubles is
+// the correctly rounded IEEE division: no fast-math option is given to this build), rounded once to float32.
+// A non-finite input sets *flag with a plain store (every thread that stores writes the same 1).
+template <int VEC>
+__global__ __launch_bounds__(256) void wld_scene_height_kernel(const float* __restrict__ chunk, int C, int K, int r0, int c0,
+                                                               int nr, int nc, int grey, float* __restrict__ dst, int W,
+                                                               int y, int x, int* __restrict__ flag) {
+    const int per_row = nc / VEC;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)nr * per_row) return;
+    const int r = (int)(idx / per_row);
+    const int xo = (int)(idx - (long)r * per_row) * VEC;
+    float q[3][VEC];
+    bool bad = false;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        if (ch >= C) break;
+        const float* sp = chunk + ((long)ch * K + r0 + r) * K + c0 + xo;
+        if constexpr (VEC == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(sp);
+            q[ch][0] = t.x; q[ch][1] = t.y; q[ch][2] = t.z; q[ch][3] = t.w;
+        } else {
+            q[ch][0] = sp[0];
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            bad = bad || !isfinite(q[ch][k]);
+            q[ch][k] = wld_unit(q[ch][k], grey);
+        }
+    }
+    float v[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+        v[k] = C == 1 ? q[0][k] : (float)((((double)q[0][k] + (double)q[1][k]) + (double)q[2][k]) / 3.0);
+    float* dp = dst + (long)(y + r) * W + x + xo;
+    if constexpr (VEC == 4)
+        *reinterpret_cast<float4*>(dp) = make_float4(v[0], v[1], v[2], v[3]);
+    else
+        dp[0] = v[0];
+    if (bad) *flag = 1;
+}
+
 // the tiles of one forward batch, passed by value: the launch carries its own table, nothing is uploaded
 struct WTiles {
     ghm_world_tile t[GHM_WORLD_MAX_TILES];
@@ -273,6 +329,30 @@ int ghm_world_crop(ghm_ctx* ctx, const float* chunk, int32_t C, int32_t K, int32
     } else {
         hipLaunchKernelGGL(wld_crop_kernel<1>, EW_GRID((long)planes * nr * nc), chunk, C, K, r0, c0, nr, nc, out_u8 ? 1 : 0,
                            grey ? 1 : 0, dst, pitch, xoff);
+    }
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+int ghm_world_scene_height(ghm_ctx* ctx, const float* chunk, int32_t C, int32_t K, int32_t r0, int32_t c0, int32_t nr,
+                           int32_t nc, int32_t grey, float* dst, int32_t H, int32_t W, int32_t y, int32_t x, int32_t* flag) {
+    GHM_CHECK(chunk && dst && flag && (C == 1 || C == 3) && K >= 1, "ghm_world_scene_height: bad arguments (C=%d K=%d)", C, K);
+    GHM_CHECK(r0 >= 0 && c0 >= 0 && nr >= 0 && nc >= 0 && (int64_t)r0 + nr <= K && (int64_t)c0 + nc <= K,
+              "ghm_world_scene_height: [%d, %d) x [%d, %d) outside the chunk of %d", r0, r0 + nr, c0, c0 + nc, K);
+    GHM_CHECK(H >= 1 && W >= 1 && y >= 0 && x >= 0 && (int64_t)y + nr <= H && (int64_t)x + nc <= W,
+              "ghm_world_scene_height: rows [%d, %d) x columns [%d, %d) outside the scene of %d x %d", y, y + nr, x, x + nc, H,
+              W);
+    GHM_CHECK((int64_t)C * K * K < ((int64_t)1 << 31) && (int64_t)H * W < ((int64_t)1 << 31),
+              "ghm_world_scene_height: too large");
+    if (nr == 0 || nc == 0) return 0;
+    // 16-byte groups need every row of both sides to start on one: a scene snapped to multiples of 4 (a flight's windows)
+    // takes this form, any other rectangle the scalar one, whose rows are just as contiguous
+    if (K % 4 == 0 && c0 % 4 == 0 && nc % 4 == 0 && W % 4 == 0 && x % 4 == 0 && al16(chunk) && al16(dst)) {
+        hipLaunchKernelGGL(wld_scene_height_kernel<4>, EW_GRID((long)nr * (nc / 4)), chunk, C, K, r0, c0, nr, nc,
+                           grey ? 1 : 0, dst, W, y, x, flag);
+    } else {
+        hipLaunchKernelGGL(wld_scene_height_kernel<1>, EW_GRID((long)nr * nc), chunk, C, K, r0, c0, nr, nc, grey ? 1 : 0, dst,
+                           W, y, x, flag);
     }
     GHM_LAUNCH_CHECK();
     return 0;

@@ -1044,6 +1044,13 @@ class Ops:
         call("ghm_texture_finalize", self.h, C.c_void_p(int(acc_ptr)), W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x,
              overlap, int(out_u8), int(b_grey), C.c_void_p(int(out_ptr)))
 
+    def texture_finalize_scene(self, acc_ptr, W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x, overlap, b_grey, tex_ptr, H, Ws,
+                               flag_ptr):
+        """texture_finalize's fp32 values of the same rows, mapped to [0, 1] as render.Scene maps a texture, -> rows
+        yc0 + r0 + ... of the scene texture fp32 [3, H, Ws] at tex_ptr; a non-finite value sets the int32 at flag_ptr"""
+        call("ghm_texture_finalize_scene", self.h, _vp(acc_ptr), W, T, Cc, r0, nrows, yc0, ny, pad_y, nx, pad_x, overlap,
+             int(b_grey), _vp(tex_ptr), H, Ws, _vp(flag_ptr))
+
     # heightmaps of any size (csrc/terrain.hip, gan_heightmaps_amd/terrain.py)
     def terrain_seed(self, P, gy, gx, s, row0, rows, blend, dst):
         """canvas seed rows [row0, row0 + rows) of the per-cell maps P [gy gx, C s s] -> dst [1, C, rows, s gx]"""
@@ -1076,6 +1083,13 @@ class Ops:
         buffer at out_ptr (rows of ``pitch`` pixels): fp32 [Cc, nr, pitch] or uint8 [nr, pitch] / [nr, pitch, 3]"""
         call("ghm_world_crop", self.h, C.c_void_p(int(chunk_ptr)), Cc, K, r0, c0, nr, nc, int(out_u8), int(grey),
              C.c_void_p(int(out_ptr)), pitch, xoff)
+
+    def world_scene_height(self, chunk_ptr, Cc, K, r0, c0, nr, nc, grey, hm_ptr, H, W, y, x, flag_ptr):
+        """rows [r0, r0 + nr) x columns [c0, c0 + nc) of a chunk [Cc, K, K], mapped to [0, 1] as render.Scene maps a
+        heightmap (three channels: their mean), -> rows [y, y + nr) x columns [x, x + nc) of the scene's height plane fp32
+        [H, W] at hm_ptr; a non-finite input sets the int32 at flag_ptr"""
+        call("ghm_world_scene_height", self.h, _vp(chunk_ptr), Cc, K, r0, c0, nr, nc, int(grey), _vp(hm_ptr), H, W, y, x,
+             _vp(flag_ptr))
 
     def world_gather(self, tiles, K, dst):
         """tiles: [((p00, p01, p10, p11), y0, x0)] -- chunk pointers [Cc, K, K] (0 where the tile does not reach) and the

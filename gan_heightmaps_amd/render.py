@@ -9,12 +9,13 @@
 
 A ``Scene`` uploads the two arrays once and builds the maximum pyramid once; every ``render`` after that is one launch and one
 download.  ``Pix2Pix.render_terrain`` renders arrays the caller has, ``TerrainWorld.scene`` / ``TerrainWorld.view`` render the
-unbounded world (the scene is assembled through the host: ``both`` -> upload).
+unbounded world (the scene is assembled through the host: ``both`` -> upload; ``TerrainWorld.scene(resident=True)`` and
+``TerrainWorld.flight`` assemble it on the device from the resident chunks).
 
     python -m gan_heightmaps_amd.render OUT.png (--heightmap F --texture F | --world EXPERIMENT MODEL --seed N
         [--chunk-cells C] [--blend B] [--dtype D]) --pos Y,X,Z (--look-at Y,X,Z | --yaw A --pitch A) [--fov DEG]
         [--size HxW] [--max-dist N] [--height-scale S] [--sun AZ,EL] [--no-shadows] [--haze V] [--step V]
-        [--frames N --to Y,X,Z]
+        [--frames N --to Y,X,Z [--window-mb M]]
 """
 import argparse
 import math
@@ -195,6 +196,45 @@ class Scene:
             self.close()
             raise
 
+    @classmethod
+    def from_device(cls, dev, hm_ptr, tex_ptr, H, W, origin=(0, 0), height_scale=DEFAULTS['height_scale']):
+        """a Scene over two buffers that are already on ``dev`` and already hold what the constructor would upload: hm fp32
+        [H, W] in [0, 1] and tex fp32 [3, H, W] in [0, 1], both allocated with dev.alloc.  The scene takes ownership of them
+        (close() frees them, and so does a failure in here); nothing is uploaded, the pyramid is built as usual."""
+        self = cls.__new__(cls)
+        self.dev, self._own = dev, False
+        self._hm, self._tex, self._mip = hm_ptr, tex_ptr, None
+        self._outbuf, self._outbytes = None, 0
+        try:
+            if len(tuple(origin)) != 2 or not all(_is_int(v) for v in origin):
+                raise ValueError("origin must be two integers (Y0, X0), got %r" % (origin,))
+            if not _num(height_scale) or height_scale <= 0:
+                raise ValueError("height_scale must be a positive number, got %r" % (height_scale,))
+            if not _is_int(H) or not _is_int(W) or H < 2 or W < 2 or H * W >= 1 << 31:
+                raise ValueError("a scene is at least 2 x 2 and below 2^31 pixels, got %r x %r" % (H, W))
+            if not hm_ptr or not tex_ptr:
+                raise ValueError("from_device needs the two device buffers")
+            from .device import Ops
+            self.origin = (int(origin[0]), int(origin[1]))
+            self.height_scale = float(height_scale)
+            self.shape = (int(H), int(W))
+            self.ops = Ops(dev)
+            self._mip = self.ops.render_maxmip(self._hm, self.shape[0], self.shape[1])
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    def arrays(self):
+        """the scene's planes as the renderer reads them, downloaded: (hm [H, W], tex [3, H, W]), float32 in [0, 1]"""
+        if self.dev is None:
+            raise ValueError("this Scene is closed")
+        H, W = self.shape
+        hm, tex = np.empty((H, W), np.float32), np.empty((3, H, W), np.float32)
+        self.dev.d2h(hm, self._hm, hm.nbytes)
+        self.dev.d2h(tex, self._tex, tex.nbytes)
+        return hm, tex
+
     def __enter__(self):
         return self
 
@@ -335,6 +375,9 @@ def parse_args(argv):
     p.add_argument("--step", type=float, default=DEFAULTS['step'], help="distance between samples")
     p.add_argument("--frames", type=int, default=None, help="render N frames, moving the camera to --to")
     p.add_argument("--to", type=_triple, default=None, metavar="Y,X,Z", help="the camera's position in the last frame")
+    p.add_argument("--window-mb", type=float, default=None, metavar="M",
+                   help="with --world and --frames: render the path through TerrainWorld.flight, from scene windows of at "
+                        "most M MiB built on the device one after the other (default: one scene over the whole path)")
     # a value that starts with a minus sign would read as an option: hand it over in the --opt=value form
     argv = list(argv)
     i = 0
@@ -375,6 +418,10 @@ def parse_args(argv):
         p.error("--frames and --to go together")
     if a.frames is not None and a.frames < 2:
         p.error("--frames must be >= 2")
+    if a.window_mb is not None and (a.world is None or a.frames is None):
+        p.error("--window-mb needs --world and --frames")
+    if a.window_mb is not None and not a.window_mb > 0:
+        p.error("--window-mb must be > 0")
     if not a.output.endswith(".png"):
         p.error("the output must be a .png")
     return a
@@ -424,6 +471,13 @@ def main(argv=None):
             model.load_model(a.world[1], mode='both')
             wkw = {k: v for k, v in (("chunk_cells", a.chunk_cells), ("blend", a.blend)) if v is not None}
             world = model.terrain_world(a.seed, **wkw)
+            if a.window_mb is not None:
+                # a window after the other, each built on the device: memory does not grow with the path
+                fkw = {k: v for k, v in kw.items() if k != "max_dist"}
+                for name, img in zip(frame_names(a), world.flight(cams, a.max_dist, window_mb=a.window_mb,
+                                                                  height_scale=a.height_scale, **fkw)):
+                    _save_png(name, img)
+                return 0
             # one scene over the union of the frames' footprints
             scene = world.scene(*union_footprint([c.footprint(a.max_dist) for c in cams]), height_scale=a.height_scale)
         else:

@@ -21,6 +21,10 @@ Textures: U-Net tiles of T = in_shp pixels are anchored to the world too, tile (
 Tex = sum(w U(tile)) / sum(w) in row-major tile order.  Tile q of a tile row always runs in slot q mod batch_size of its
 forward pass.  The tiles are gathered on the device from the resident chunks: the heightmap never visits the host.
 
+Rendering: ``scene`` hands a rectangle to the ray caster -- through the host, or with resident=True
+assembled on the device by sinks that write a render.Scene's planes --, and ``flight`` renders a camera path of any length
+from one bounded scene window after the other (``flight_plan``: the window rule).
+
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]]
 """
@@ -36,8 +40,9 @@ from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
 from . import terrain as _terrain
 from .texture import check_overlap
 
-__all__ = ["HEAD_BLOCK", "MAX_BATCH", "world_latent", "axis_chunks", "axis_tiles", "seed_cells", "window_elements",
-           "default_chunk_cells", "slot_batches", "TerrainWorld", "parse_region", "parse_args", "main"]
+__all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
+           "window_elements", "default_chunk_cells", "slot_batches", "snap_out", "plan_windows", "TerrainWorld", "parse_region",
+           "parse_args", "main"]
 
 HEAD_BLOCK = 8                   # the head runs over world-aligned blocks of HEAD_BLOCK x HEAD_BLOCK cells, one pass each
 MAX_BATCH = 32                   # GHM_WORLD_MAX_TILES (include/ghm.h): tiles per forward pass
@@ -103,6 +108,209 @@ def slot_batches(q_lo, q_hi, B):
         lo, hi = max(B * k, q_lo), min(B * k + B - 1, q_hi)
         out.append(([min(max(B * k + j, q_lo), q_hi) for j in range(B)], lo - B * k, hi - lo + 1))
     return out
+
+
+# bytes of device memory a render scene keeps per pixel: the height plane (4), the three texture planes (12) and
+# the maximum pyramid (4/3 of the map, 16/3 bytes), rounded up
+SCENE_BYTES_PER_PIXEL = 22
+
+
+def snap_out(rect, snap):
+    """the rectangle (y0, x0, h, w) expanded outward to multiples of ``snap`` (floor and ceiling, so negative coordinates move
+    away from zero as positive ones do)"""
+    y0, x0, h, w = rect
+    ya, xa = y0 // snap * snap, x0 // snap * snap
+    yb, xb = -(-(y0 + h) // snap) * snap, -(-(x0 + w) // snap) * snap
+    return ya, xa, yb - ya, xb - xa
+
+
+def plan_windows(footprints, snap, max_pixels):
+    """the scene windows of a camera path: [(rect, first_frame, last_frame)].  Starting at frame i a window takes the longest
+    run of consecutive frames i .. j whose footprints' union, expanded outward to multiples of ``snap``, has at most
+    ``max_pixels`` pixels; the next window starts at j + 1.  A frame whose own snapped footprint is larger is a ValueError."""
+    if not _is_int(snap) or snap < 1:
+        raise ValueError("snap must be a positive integer, got %r" % (snap,))
+    out, i, n = [], 0, len(footprints)
+    while i < n:
+        rect = snap_out(footprints[i], snap)
+        if rect[2] * rect[3] > max_pixels:
+            raise ValueError("frame %d alone needs a window of %d x %d = %d pixels, the cap is %d: raise window_mb"
+                             % (i, rect[2], rect[3], rect[2] * rect[3], max_pixels))
+        j = i
+        while j + 1 < n:
+            f = footprints[j + 1]
+            y0, x0 = min(rect[0], f[0]), min(rect[1], f[1])
+            y1, x1 = max(rect[0] + rect[2], f[0] + f[2]), max(rect[1] + rect[3], f[1] + f[3])
+            grown = snap_out((y0, x0, y1 - y0, x1 - x0), snap)
+            if grown[2] * grown[3] > max_pixels:
+                break
+            rect, j = grown, j + 1
+        out.append((rect, i, j))
+        i = j + 1
+    return out
+
+
+class _HostSinks:
+    """Where a request's finished rows go, the host form: a device stage -> a pinned buffer -> the caller's arrays, two of each
+    per output, the downloads on a copy stream of their own so that finished rows go down while the next chunks run."""
+
+    def __init__(self, world, rect, alloc, out_hm, out_tex, hm_u8, tex_u8):
+        self.world, self.rect, self.alloc = world, rect, alloc
+        self.out_hm, self.out_tex, self.hm_u8, self.tex_u8 = out_hm, out_tex, hm_u8, tex_u8
+        self.cp = type(world._dev)(world._dev.index)
+        self.pins, self.events = [], []
+        self.hdone, self.hpending, self.tpending, self.finals = [], [], [], 0
+
+    def _pinned(self, n):
+        from .device import PinnedArray
+        self.pins.append(PinnedArray((n,), np.uint8))
+        return self.pins[-1]
+
+    def _event(self, d):
+        self.events.append(d.event_create())
+        return self.events[-1]
+
+    def begin_hm(self):
+        wd, (y0, x0, h, w) = self.world, self.rect
+        C, dev = wd._geo.channels, wd._dev
+        self.hbpp = (1 if C == 1 else 3) if self.hm_u8 else 4 * C
+        hrows = min(wd._K, h)
+        self.hstage = [self.alloc(dev, hrows * w * self.hbpp) for _ in range(2)]
+        self.hpin = [self._pinned(hrows * w * self.hbpp) for _ in range(2)]
+        self.hfin, self.hdown = [self._event(dev) for _ in range(2)], [self._event(self.cp) for _ in range(2)]
+
+    def begin_tex(self, c_out, Wp):
+        wd = self.world
+        T, udev = wd._geo.out, wd._udev
+        self.c_out, self.Wp = c_out, Wp
+        self.tbpp = 3 if self.tex_u8 else 4 * c_out
+        self.tstage = [self.alloc(udev, T * Wp * self.tbpp) for _ in range(2)]
+        self.tpin = [self._pinned(T * Wp * self.tbpp) for _ in range(2)]
+        self.tfin, self.tdown = [self._event(udev) for _ in range(2)], [self._event(self.cp) for _ in range(2)]
+
+    def _hm_drain(self, item):
+        slot, ya, yb = item
+        C, w, out_hm = self.world._geo.channels, self.rect[3], self.out_hm
+        self.world._dev.event_sync(self.hdown[slot])
+        k = yb - ya
+        a = self.hpin[slot].array[:k * w * self.hbpp]
+        if not self.hm_u8:
+            out_hm[:, ya:yb, :] = a.view(np.float32).reshape(C, k, w)
+        elif C == 1:
+            out_hm[ya:yb] = a.reshape(k, w)
+        else:
+            out_hm[ya:yb] = a.reshape(k, w, 3)
+
+    def hm_row(self, a, b_lo, b_hi):
+        """the request's rows inside chunk row a (its chunks are resident) -> a stage -> the host"""
+        wd, (y0, x0, h, w), cp = self.world, self.rect, self.cp
+        dev, ops, K, C = wd._dev, wd._ops, wd._K, wd._geo.channels
+        slot = len(self.hdone) % 2
+        ra, rb = max(y0, a * K), min(y0 + h, (a + 1) * K)
+        if len(self.hdone) >= 2:
+            dev.event_wait(self.hdown[slot])                 # the stage's previous download has left
+        for b in range(b_lo, b_hi + 1):
+            ca, cb = max(x0, b * K), min(x0 + w, (b + 1) * K)
+            ops.world_crop(wd._chunks[(a, b)], C, K, ra - a * K, ca - b * K, rb - ra, cb - ca, self.hm_u8,
+                           wd.model.is_a_grayscale, self.hstage[slot], w, ca - x0)
+        dev.event_record(self.hfin[slot])
+        cp.event_wait(self.hfin[slot])
+        cp.d2h_async(self.hpin[slot], self.hstage[slot], (rb - ra) * w * self.hbpp)
+        cp.event_record(self.hdown[slot])
+        self.hdone.append(a)
+        self.hpending.append((slot, ra - y0, rb - y0))
+        while len(self.hpending) > 1:
+            self._hm_drain(self.hpending.pop(0))
+
+    def _tex_drain(self, item):
+        slot, ya, yb = item
+        c_out, Wp, w, out_tex = self.c_out, self.Wp, self.rect[3], self.out_tex
+        self.world._udev.event_sync(self.tdown[slot])
+        n = yb - ya
+        if self.tex_u8:
+            out_tex[ya:yb] = self.tpin[slot].array[:n * Wp * 3].reshape(n, Wp, 3)[:, :w]
+        else:
+            out_tex[:, ya:yb, :] = self.tpin[slot].array[:c_out * n * Wp * 4].view(np.float32) \
+                .reshape(c_out, n, Wp)[:, :, :w]
+
+    def tex_rows(self, acc, r_lo, n, yr, ny, pad_y, nx, pad_x):
+        """rows [r_lo, r_lo + n) of the accumulator, the request's rows yr + r_lo ..., finalized -> a stage -> the host"""
+        wd, cp = self.world, self.cp
+        udev = wd._udev
+        slot = self.finals % 2
+        if self.finals >= 2:
+            udev.event_wait(self.tdown[slot])
+        wd._uops.texture_finalize(acc, self.Wp, wd._geo.out, self.c_out, r_lo, n, yr, ny, pad_y, nx, pad_x, wd.overlap,
+                                  self.tex_u8, wd.model.is_b_grayscale, self.tstage[slot])
+        udev.event_record(self.tfin[slot])
+        cp.event_wait(self.tfin[slot])
+        cp.d2h_async(self.tpin[slot], self.tstage[slot], n * self.Wp * self.tbpp)
+        cp.event_record(self.tdown[slot])
+        self.tpending.append((slot, yr + r_lo, yr + r_lo + n))
+        self.finals += 1
+
+    def tex_poll(self):
+        while len(self.tpending) > 1:
+            self._tex_drain(self.tpending.pop(0))
+
+    def finish(self):
+        while self.tpending:
+            self._tex_drain(self.tpending.pop(0))
+        while self.hpending:
+            self._hm_drain(self.hpending.pop(0))
+
+    def close(self):
+        self.cp.sync()
+        for e in self.events:
+            self.world._dev.event_destroy(e)
+        for p in self.pins:
+            p.close()
+        self.cp.close()
+
+
+class _SceneSinks:
+    """Where a request's finished rows go, the resident form: straight into the planes of a render scene on the
+    device -- hm fp32 [h, w] at hm_ptr, tex fp32 [3, h, w] at tex_ptr, mapped to [0, 1] by the sinks' kernels as render.Scene
+    maps them on the host.  No stage, no pinned buffer, no copy stream; a non-finite value sets the int32 at flag_ptr."""
+
+    def __init__(self, world, rect, hm_ptr, tex_ptr, flag_ptr):
+        self.world, self.rect = world, rect
+        self.hm_ptr, self.tex_ptr, self.flag_ptr = hm_ptr, tex_ptr, flag_ptr
+        self.hdone = []
+
+    def begin_hm(self):
+        if self.world._geo.channels not in (1, 3):
+            raise ValueError("a scene needs a 1- or 3-channel heightmap generator, this one has %d"
+                             % self.world._geo.channels)
+
+    def begin_tex(self, c_out, Wp):
+        if c_out not in (1, 3):
+            raise ValueError("a scene needs a 1- or 3-channel texture generator, this one has %d" % c_out)
+        self.c_out, self.Wp = c_out, Wp
+
+    def hm_row(self, a, b_lo, b_hi):
+        wd, (y0, x0, h, w) = self.world, self.rect
+        K = wd._K
+        ra, rb = max(y0, a * K), min(y0 + h, (a + 1) * K)
+        for b in range(b_lo, b_hi + 1):
+            ca, cb = max(x0, b * K), min(x0 + w, (b + 1) * K)
+            wd._ops.world_scene_height(wd._chunks[(a, b)], wd._geo.channels, K, ra - a * K, ca - b * K, rb - ra, cb - ca,
+                                       wd.model.is_a_grayscale, self.hm_ptr, h, w, ra - y0, ca - x0, self.flag_ptr)
+        self.hdone.append(a)
+
+    def tex_rows(self, acc, r_lo, n, yr, ny, pad_y, nx, pad_x):
+        wd, (y0, x0, h, w) = self.world, self.rect
+        wd._uops.texture_finalize_scene(acc, self.Wp, wd._geo.out, self.c_out, r_lo, n, yr, ny, pad_y, nx, pad_x, wd.overlap,
+                                        wd.model.is_b_grayscale, self.tex_ptr, h, w, self.flag_ptr)
+
+    def tex_poll(self):
+        pass
+
+    def finish(self):
+        pass
+
+    def close(self):
+        pass
 
 
 class TerrainWorld:
@@ -348,13 +556,79 @@ class TerrainWorld:
         """(heightmap, texture) of one rectangle from one pass over the chunks; bit for bit the two separate calls"""
         return self._request(y0, x0, h, w, True, True, out_heightmap, out_texture, uint8, uint8)
 
-    def scene(self, y0, x0, h, w, **kw):
+    def scene(self, y0, x0, h, w, resident=False, **kw):
         """the rectangle as a render.Scene with origin (y0, x0): ``both`` in float32, uploaded once.  Cameras are
-        given in world coordinates.  kw: height_scale.  Close it, or use it as a context manager."""
+        given in world coordinates.  kw: height_scale.  Close it, or use it as a context manager.
+        resident=True assembles the same scene on the device: the chunks' and the accumulator's rows are mapped
+        and written straight into the scene's planes, nothing visits the host; the planes, and so every render, are bit for
+        bit the default's."""
         from .render import Scene
+        if resident:
+            return self._resident_scene(y0, x0, h, w, **kw)
         hm, tex = self.both(y0, x0, h, w)
         return Scene(hm, tex, origin=(y0, x0), value_range=(self.model.is_a_grayscale, self.model.is_b_grayscale),
                      device=self.model.device, **kw)
+
+    def _resident_scene(self, y0, x0, h, w, **kw):
+        from .render import Scene
+        y0, x0, h, w = self._check_region(y0, x0, h, w)
+        if h < 2 or w < 2 or h * w >= 1 << 31:
+            raise ValueError("a scene is at least 2 x 2 and below 2^31 pixels, got %d x %d" % (h, w))
+        if self._closed:
+            raise ValueError("this TerrainWorld is closed")
+        dev = self.model.device
+        bufs = []
+        try:
+            for n in (4 * h * w, 12 * h * w, 4):                  # the height plane, the three texture planes, the flag
+                bufs.append(dev.alloc(n))
+            hm, tex, flag = bufs
+            dev.memset_zero(flag, 4)
+            dev.sync()
+            self._request(y0, x0, h, w, True, True, None, None, False, False, scene=(hm, tex, flag))
+            seen = np.zeros(1, np.int32)
+            dev.d2h(seen, flag, 4)
+            if seen[0]:
+                raise ValueError("the heightmap or the texture has non-finite values")
+        except Exception:
+            for p in bufs:
+                dev.free(p)
+            raise
+        dev.free(flag)
+        return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), **kw)
+
+    def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None):
+        """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
+        device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
+        consecutive frames i .. j such that the union of their footprints, expanded outward to multiples of ``snap``
+        (default in_shp), has at most max_pixels = floor(window_mb 2^20 / 22) pixels: a scene keeps 22 bytes per pixel
+        (SCENE_BYTES_PER_PIXEL: 4 of height, 12 of texture, 16/3 of pyramid, rounded up).  The next window starts at j + 1.  A
+        frame whose own snapped footprint exceeds the cap is a ValueError.  Deterministic in its arguments alone."""
+        if isinstance(window_mb, bool) or not isinstance(window_mb, (int, float, np.integer, np.floating)) \
+                or not window_mb > 0:
+            raise ValueError("window_mb must be a number > 0, got %r" % (window_mb,))
+        snap = self._geo.out if snap is None else snap
+        return plan_windows([c.footprint(max_dist) for c in cameras], snap,
+                            int(window_mb * (1 << 20)) // SCENE_BYTES_PER_PIXEL)
+
+    def flight(self, cameras, max_dist, window_mb=1024, snap=None, height_scale=None, **render_kw):
+        """the images of a camera path of any length, one per camera and in order, from bounded device memory:
+        for each window of flight_plan one resident scene is built, its frames are rendered (one launch and one download
+        each), and it is closed before the next is built; chunks that consecutive windows share come from the cache.
+        Frame k is bit for bit Scene(*world.both(*rect), origin=rect[:2], ...).render(cameras[k], max_dist=max_dist, ...)
+        for its window's rect.  The plan is made, and its refusals raised, by this call; the device works as the returned
+        generator is consumed.  render_kw: Scene.render's."""
+        cameras = list(cameras)
+        if self._closed:
+            raise ValueError("this TerrainWorld is closed")
+        plan = self.flight_plan(cameras, max_dist, window_mb, snap)
+        skw = {} if height_scale is None else {"height_scale": height_scale}
+
+        def frames():
+            for rect, i, j in plan:
+                with self.scene(*rect, resident=True, **skw) as scene:
+                    for k in range(i, j + 1):
+                        yield scene.render(cameras[k], max_dist=max_dist, **render_kw)
+        return frames()
 
     def view(self, camera, max_dist, height_scale=None, **kw):
         """one image of the world from ``camera`` (world coordinates, negative ones included), rays ``max_dist`` long: the
@@ -363,18 +637,19 @@ class TerrainWorld:
         with self.scene(*camera.footprint(max_dist), **skw) as scene:
             return scene.render(camera, max_dist=max_dist, **kw)
 
-    def _request(self, y0, x0, h, w, want_hm, want_tex, out_hm, out_tex, hm_u8, tex_u8):
-        from .device import PinnedArray
+    def _request(self, y0, x0, h, w, want_hm, want_tex, out_hm, out_tex, hm_u8, tex_u8, scene=None):
+        """the chunks, the tiles and the accumulator of one rectangle; finished rows leave through a sink: the host's arrays
+        (_HostSinks), or with scene=(hm_ptr, tex_ptr, flag_ptr) the device planes of a render scene (_SceneSinks)"""
         y0, x0, h, w = self._check_region(y0, x0, h, w)
-        geo, K, m = self._geo, self._K, self.model
+        geo, K = self._geo, self._K
         C = geo.channels
-        if want_hm:
+        if want_hm and scene is None:
             if hm_u8 and C not in (1, 3):
                 raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % C)
             shape = ((h, w) if C == 1 else (h, w, 3)) if hm_u8 else (C, h, w)
             out_hm = self._out(out_hm, shape, np.uint8 if hm_u8 else np.float32)
         self._bind()
-        eng, dev, ops, udev, uops = self._eng, self._dev, self._ops, self._udev, self._uops
+        eng, udev, uops = self._eng, self._udev, self._uops
         T, o, B = geo.out, self.overlap, self.batch_size
         st = T - o
         if want_tex:
@@ -384,72 +659,31 @@ class TerrainWorld:
             if (inp.H, inp.W, u.H, u.W) != (T, T, T, T) or inp.Cc != C:
                 raise ValueError("the pix2pix generator takes %d x %d x %d tiles, the heightmap generator makes %d x %d x %d"
                                  % (inp.Cc, inp.H, inp.W, C, T, T))
-            if tex_u8 and c_out not in (1, 3):
-                raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % c_out)
-            out_tex = self._out(out_tex, (h, w, 3) if tex_u8 else (c_out, h, w), np.uint8 if tex_u8 else np.float32)
+            if scene is None:
+                if tex_u8 and c_out not in (1, 3):
+                    raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % c_out)
+                out_tex = self._out(out_tex, (h, w, 3) if tex_u8 else (c_out, h, w), np.uint8 if tex_u8 else np.float32)
         a_lo, a_hi = axis_chunks(y0, h, K)
         b_lo, b_hi = axis_chunks(x0, w, K)
         eng.sync()
-        cp = type(dev)(dev.index)                # the copy stream: finished rows go down while the next chunks run
-        devbufs, pins, events = [], [], []
+        devbufs = []
 
         def alloc(d, n):
             devbufs.append((d, d.alloc(n)))
             return devbufs[-1][1]
 
-        def pinned(n):
-            pins.append(PinnedArray((n,), np.uint8))
-            return pins[-1]
-
-        def event(d):
-            events.append(d.event_create())
-            return events[-1]
-
+        if scene is None:
+            sink = _HostSinks(self, (y0, x0, h, w), alloc, out_hm, out_tex, hm_u8, tex_u8)
+        else:
+            sink = _SceneSinks(self, (y0, x0, h, w), *scene)
         try:
-            # ---- heightmap rows: one stage per chunk row ----
+            # ---- heightmap rows: one sink call per chunk row ----
             if want_hm:
-                hbpp = (1 if C == 1 else 3) if hm_u8 else 4 * C
-                hrows = min(K, h)
-                hstage = [alloc(dev, hrows * w * hbpp) for _ in range(2)]
-                hpin = [pinned(hrows * w * hbpp) for _ in range(2)]
-                hfin, hdown = [event(dev) for _ in range(2)], [event(cp) for _ in range(2)]
-            hpending, hdone = [], []
-
-            def hm_drain(item):
-                slot, ya, yb = item
-                dev.event_sync(hdown[slot])
-                k = yb - ya
-                a = hpin[slot].array[:k * w * hbpp]
-                if not hm_u8:
-                    out_hm[:, ya:yb, :] = a.view(np.float32).reshape(C, k, w)
-                elif C == 1:
-                    out_hm[ya:yb] = a.reshape(k, w)
-                else:
-                    out_hm[ya:yb] = a.reshape(k, w, 3)
-
-            def hm_row(a):
-                """the request's rows inside chunk row a (its chunks are resident) -> a stage -> the host"""
-                slot = len(hdone) % 2
-                ra, rb = max(y0, a * K), min(y0 + h, (a + 1) * K)
-                if len(hdone) >= 2:
-                    dev.event_wait(hdown[slot])              # the stage's previous download has left
-                for b in range(b_lo, b_hi + 1):
-                    ca, cb = max(x0, b * K), min(x0 + w, (b + 1) * K)
-                    ops.world_crop(self._chunks[(a, b)], C, K, ra - a * K, ca - b * K, rb - ra, cb - ca, hm_u8,
-                                   m.is_a_grayscale, hstage[slot], w, ca - x0)
-                dev.event_record(hfin[slot])
-                cp.event_wait(hfin[slot])
-                cp.d2h_async(hpin[slot], hstage[slot], (rb - ra) * w * hbpp)
-                cp.event_record(hdown[slot])
-                hdone.append(a)
-                hpending.append((slot, ra - y0, rb - y0))
-                while len(hpending) > 1:
-                    hm_drain(hpending.pop(0))
-
+                sink.begin_hm()
             if not want_tex:
                 for a in range(a_lo, a_hi + 1):
                     self._acquire([(a, b) for b in range(b_lo, b_hi + 1)])
-                    hm_row(a)
+                    sink.hm_row(a, b_lo, b_hi)
             else:
                 # ---- texture: §4j's executor over world-anchored tiles, as the interior of a plan one tile larger ----
                 p_lo, p_hi = axis_tiles(y0, h, T, o)
@@ -459,24 +693,10 @@ class TerrainWorld:
                 Wp = (w + 3) // 4 * 4                         # whole 16-byte groups per accumulator row
                 tb_lo, tb_hi = (q_lo * st) // K, (q_hi * st + T - 1) // K
                 batches = slot_batches(q_lo, q_hi, B)
-                tbpp = 3 if tex_u8 else 4 * c_out
                 acc_bytes = c_out * T * Wp * 4
                 acc = alloc(udev, acc_bytes)
-                tstage = [alloc(udev, T * Wp * tbpp) for _ in range(2)]
-                tpin = [pinned(T * Wp * tbpp) for _ in range(2)]
-                tfin, tdown = [event(udev) for _ in range(2)], [event(cp) for _ in range(2)]
+                sink.begin_tex(c_out, Wp)
                 udev.memset_zero(acc, acc_bytes)
-                tpending, finals = [], 0
-
-                def tex_drain(item):
-                    slot, ya, yb = item
-                    udev.event_sync(tdown[slot])
-                    n = yb - ya
-                    if tex_u8:
-                        out_tex[ya:yb] = tpin[slot].array[:n * Wp * 3].reshape(n, Wp, 3)[:, :w]
-                    else:
-                        out_tex[:, ya:yb, :] = tpin[slot].array[:c_out * n * Wp * 4].view(np.float32) \
-                            .reshape(c_out, n, Wp)[:, :, :w]
 
                 for p in range(p_lo, p_hi + 1):
                     ty = p * st
@@ -484,8 +704,8 @@ class TerrainWorld:
                     self._acquire([(a, b) for a in range(ta_lo, ta_hi + 1) for b in range(tb_lo, tb_hi + 1)])
                     if want_hm:
                         for a in range(max(ta_lo, a_lo), min(ta_hi, a_hi) + 1):
-                            if a not in hdone:
-                                hm_row(a)
+                            if a not in sink.hdone:
+                                sink.hm_row(a, b_lo, b_hi)
                     for qs, slot0, nb in batches:
                         tiles = []
                         for q in qs:
@@ -507,17 +727,7 @@ class TerrainWorld:
                     yr = ty - y0
                     r_lo, r_hi = max(0, -yr), min(T if last else st, h - yr)
                     if r_hi > r_lo:
-                        slot = finals % 2
-                        if finals >= 2:
-                            udev.event_wait(tdown[slot])
-                        uops.texture_finalize(acc, Wp, T, c_out, r_lo, r_hi - r_lo, yr, ny, pad_y, nx, pad_x, o, tex_u8,
-                                              m.is_b_grayscale, tstage[slot])
-                        udev.event_record(tfin[slot])
-                        cp.event_wait(tfin[slot])
-                        cp.d2h_async(tpin[slot], tstage[slot], (r_hi - r_lo) * Wp * tbpp)
-                        cp.event_record(tdown[slot])
-                        tpending.append((slot, yr + r_lo, yr + r_hi))
-                        finals += 1
+                        sink.tex_rows(acc, r_lo, r_hi - r_lo, yr, ny, pad_y, nx, pad_x)
                     if not last:
                         row = Wp * 4
                         for c in range(c_out):
@@ -525,23 +735,14 @@ class TerrainWorld:
                             if o:
                                 udev.d2d(base, base + st * row, o * row)
                             udev.memset_zero(base + o * row, (T - o) * row)
-                    while len(tpending) > 1:
-                        tex_drain(tpending.pop(0))
-                while tpending:
-                    tex_drain(tpending.pop(0))
-            while hpending:
-                hm_drain(hpending.pop(0))
+                    sink.tex_poll()
+            sink.finish()
             eng.sync()
         finally:
             eng.sync()
-            cp.sync()
-            for e in events:
-                dev.event_destroy(e)
-            for p in pins:
-                p.close()
+            sink.close()
             for d, p in devbufs:
                 d.free(p)
-            cp.close()
             self._release()
         return out_hm, out_tex
 
