@@ -88,7 +88,8 @@ __global__ __launch_bounds__(256) void comm_f32_to_bf16_kernel(const float* __re
     if (i >= n) return;
     const unsigned u = __float_as_uint(x[i]);
     unsigned r = u + 0x7fffu + ((u >> 16) & 1u);
-    if ((u & 0x7f800000u) == 0x7f800000u) r = u;          // inf / nan keep their class (a nan stays a nan: the quiet bit is in the top half)
+    if ((u & 0x7f800000u) == 0x7f800000u) r = u;          // inf / nan keep their class ...
+    if ((u & 0x7fffffffu) > 0x7f800000u) r |= 0x00400000u;  // ... a nan whose payload lies in the low half alone gets the quiet bit
     y[i] = (unsigned short)(r >> 16);
 }
 

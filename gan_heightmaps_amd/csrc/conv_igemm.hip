@@ -1652,7 +1652,7 @@ __global__ __launch_bounds__(256) void channel_sum_partial(const float* __restri
     const long chunk = ((total + S - 1) / S + 3) & ~3L;
     const long lo = sidx * chunk, hi = min(lo + chunk, total);
     float s = 0.f;
-    if ((HW & 3) == 0 && (nstride & 3) == 0) {
+    if ((HW & 3) == 0 && (nstride & 3) == 0 && ((uintptr_t)x & 15) == 0) {     // a view at an odd element offset: the scalar loop
         // four 16-byte loads in flight per thread (one per iteration left a wave a single load deep: 2.4 TB/s on the 67 MB
         // gradients of the 256^2 layers); the four partial sums are added in a fixed order
         const float* xc = x + (long)c * HW;
