@@ -23,6 +23,14 @@ def test_trace_is_reproducible():
             assert LT.digest(a) == LT.digest(b), (name, mode)
             digests.add(LT.digest(a))
     assert len(digests) == 4        # and it tells graphs and modes apart
+    # a data-parallel step (sharded, embedded collectives) and the input pipeline: events and copies are traced too
+    todo = LT.cases()
+    for name in ("dp128/rs_ag/embedded/rank1", "pipeline128/resident"):
+        a, b = todo[name](), todo[name]()
+        assert any(r["pipe"] for r in a) and any(r["calls"] for r in a), name
+        assert LT.digest(a) == LT.digest(b), name
+        digests.add(LT.digest(a))
+    assert len(digests) == 6
 
 
 def test_unknown_value_type_is_an_error():
