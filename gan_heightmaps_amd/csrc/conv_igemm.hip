@@ -2492,6 +2492,7 @@ int ghm_conv2d_transpose_weights(ghm_ctx* ctx, const ghm_conv_desc* d, const flo
 
 int ghm_transpose_weights_batched(ghm_ctx* ctx, const void* table, int32_t n_items, int32_t total_blocks) {
     static_assert(sizeof(TransposeItem) == 32, "table layout is part of the ABI (see ghm.h)");
+    GHM_CHECK(ctx && table, "ghm_transpose_weights_batched: null argument");
     if (n_items <= 0 || total_blocks <= 0) return 0;
     hipLaunchKernelGGL(transpose_weights_batched_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream,
                        (const TransposeItem*)table, n_items);

@@ -1676,7 +1676,9 @@ int ghm_lp_weight_bytes(const ghm_conv_desc* d, int32_t transposed, size_t* byte
 
 int ghm_lp_pack_weights(ghm_ctx* ctx, const ghm_conv_desc* d, const float* wp, void* wq, int32_t dtype,
                         int32_t transposed) {
+    GHM_CHECK(ctx && d && wp && wq, "ghm_lp_pack_weights: null argument");
     GHM_CHECK(dtype == GHM_DTYPE_BF16 || dtype == GHM_DTYPE_F16, "ghm_lp_pack_weights: dtype %d", dtype);
+    GHM_CHECK(((uintptr_t)wq & 15) == 0, "ghm_lp_pack_weights: 16-byte aligned wq required (the pack is stored in 16-byte units)");
     const int T = d->kh * d->kw;
     const int red = transposed ? d->K : d->C, rows = transposed ? d->C : d->K;
     const int nblk = (red + 15) / 16 * 2, rp = rpad128(rows);
@@ -1699,6 +1701,7 @@ int ghm_lp_pack_weights(ghm_ctx* ctx, const ghm_conv_desc* d, const float* wp, v
 
 int ghm_lp_pack_batched(ghm_ctx* ctx, const void* table, int32_t n_items, int32_t total_blocks, int32_t dtype) {
     static_assert(sizeof(LpPackItem) == 48, "table layout is part of the ABI (see ghm.h)");
+    GHM_CHECK(ctx && table, "ghm_lp_pack_batched: null argument");
     GHM_CHECK(dtype == GHM_DTYPE_BF16 || dtype == GHM_DTYPE_F16, "ghm_lp_pack_batched: dtype %d", dtype);
     if (n_items <= 0 || total_blocks <= 0) return 0;
     if (dtype == GHM_DTYPE_BF16)

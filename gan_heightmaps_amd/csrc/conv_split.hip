@@ -2245,6 +2245,7 @@ int ghm_split_weight_bytes(const ghm_conv_desc* d, int32_t transposed, size_t* b
 int ghm_split_pack_weights(ghm_ctx* ctx, const ghm_conv_desc* d, const float* wp, void* wq, int32_t transposed, int32_t pieces) {
     GHM_CHECK(ctx && d && wp && wq, "null argument");
     GHM_SP_PIECES_OK(pieces);
+    GHM_CHECK(((uintptr_t)wq & 15) == 0, "ghm_split_pack_weights: 16-byte aligned wq required (the pack is stored in 16-byte units)");
     const int red = transposed ? d->K : d->C, rows = transposed ? d->C : d->K;
     const int T = d->kh * d->kw, nblk = sp_nblk(red), rpad = sp_rpad(rows);
     const long plane = (long)nblk * T * rpad;

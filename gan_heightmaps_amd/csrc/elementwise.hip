@@ -1491,6 +1491,8 @@ int ghm_upconv_collapse_weights(ghm_ctx* ctx, const float* wp5, const float* bia
 }
 
 int ghm_upconv_collapse_batched(ghm_ctx* ctx, const void* table, int32_t n_items, int32_t total_blocks) {
+    static_assert(sizeof(CollapseItem) == 48, "table layout is part of the ABI (see ghm.h)");
+    GHM_CHECK(ctx && table, "ghm_upconv_collapse_batched: null argument");
     if (n_items <= 0 || total_blocks <= 0) return 0;
     hipLaunchKernelGGL(upconv_collapse_batched_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream,
                        (const CollapseItem*)table, n_items);
@@ -1499,6 +1501,8 @@ int ghm_upconv_collapse_batched(ghm_ctx* ctx, const void* table, int32_t n_items
 }
 
 int ghm_upconv_expand_batched(ghm_ctx* ctx, const void* table, int32_t n_items, int32_t total_blocks, int32_t accumulate) {
+    static_assert(sizeof(ExpandItem) == 32, "table layout is part of the ABI (see ghm.h)");
+    GHM_CHECK(ctx && table, "ghm_upconv_expand_batched: null argument");
     if (n_items <= 0 || total_blocks <= 0) return 0;
     hipLaunchKernelGGL(upconv_expand_batched_kernel, dim3(total_blocks), dim3(256), 0, ctx->stream, (const ExpandItem*)table,
                        n_items, accumulate);

@@ -626,7 +626,11 @@ class Ops:
 
     def lp_pack_table(self, items):
         """items: [(wp DevTensor | ptr, wq ptr, red, T, rows, transposed)] -> (device table ptr, n, total blocks) for
-        lp_pack_batched (uploaded once: the pointers are fixed for the life of a plan)"""
+        lp_pack_batched (uploaded once: the pointers are fixed for the life of a plan).  The kernels store 16-byte units and the
+        entry point cannot see the device table's pointers: a wq that is not 16-byte aligned is refused here"""
+        for it in items:
+            if int(it[1]) % 16:
+                raise ValueError("lp_pack_table: wq %#x is not 16-byte aligned (the pack is stored in 16-byte units)" % int(it[1]))
         rec = np.zeros(len(items), dtype=[('wp', '<u8'), ('wq', '<u8'), ('red', '<i4'), ('T', '<i4'), ('rows', '<i4'),
                                           ('nblk', '<i4'), ('rpad', '<i4'), ('tr', '<i4'), ('b0', '<i4'), ('pad', '<i4')])
         b0 = 0

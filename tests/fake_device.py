@@ -158,6 +158,7 @@ class PolicyOps(RecordingOps):
         return 1024
 
     def lp_pack_table(self, items):
+        assert all(int(t[1]) % 16 == 0 for t in items), "device.Ops.lp_pack_table refuses a pack that is not 16-byte aligned"
         self.calls.append(("lp_pack_table", tuple((int(t[2]), int(t[3]), int(t[4]), bool(t[5])) for t in items), {}))
         return (0, len(items), 1)
 
