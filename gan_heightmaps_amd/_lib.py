@@ -189,6 +189,8 @@ SIGNATURES = {
     "ghm_adam": [_p, _p, _p, _p, _p, _i64, _p, _f, _f, _f, _f],
     "ghm_adam_tick": [_p, _p],
     "ghm_opt_update": [_p, _i32, _p, _p, _p, _p, _p, _i64, _p, _f, _f, _f, _f],
+    "ghm_ema_update": [_p, _p, _p, _i64, _f],
+    "ghm_swap_f32": [_p, _p, _p, _i64],
     "ghm_set_loss_scale_state": [_p, _p],
     "ghm_grad_check": [_p, _p, _i64],
     "ghm_loss_scale_update": [_p, _i32, _f, _f],

@@ -1160,6 +1160,14 @@ class Ops:
         call("ghm_opt_update", self.h, OPT_RULES[rule], _vp(p), _vp(g), _vp(s[0]), _vp(s[1]), _vp(s[2]), int(n), _vp(hyper),
              h[0], h[1], h[2], grad_scale)
 
+    def ema_update(self, ema, w, n, decay):
+        """ghm_ema_update: ema[:n] = decay * ema[:n] + (1 - decay) * w[:n] (skipped with the update of an overflowed fp16 step)"""
+        call("ghm_ema_update", self.h, _vp(ema), _vp(w), int(n), float(decay))
+
+    def swap_f32(self, a, b, n):
+        """ghm_swap_f32: exchange a[:n] and b[:n], bit for bit"""
+        call("ghm_swap_f32", self.h, _vp(a), _vp(b), int(n))
+
     def grad_check(self, g, n):
         call("ghm_grad_check", self.h, _vp(g), int(n))
 

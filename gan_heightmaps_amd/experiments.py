@@ -135,6 +135,11 @@ def experiment_kwargs(name):
         kw['train_mode'] = 'both'
         kw['disc_fn_p2p'] = p2p.pixel_discriminator
         kw['disc_params_p2p'] = {'nf': 64, 'bn': False, 'act': linear, 'mul_factor': [1, 2]}
+    elif name == 'test1_nobn_bilin_both_ema':
+        # test1_nobn_bilin_both with an exponential moving average of the generators' weights (not in the reference)
+        kw['gen_params_p2p'] = {'nf': 64, 'act': tanh, 'num_repeats': 0, 'bilinear_upsample': True}
+        kw['train_mode'] = 'both'
+        kw['ema'] = 0.999
     else:
         raise KeyError(name)
     return kw
@@ -214,9 +219,19 @@ def test1_nobn_bilin_both_pixeld(mode, num_epochs=1000, **kw):
     return model
 
 
+def test1_nobn_bilin_both_ema(mode, num_epochs=1000, **kw):
+    """test1_nobn_bilin_both with ema=0.999: every checkpoint N.model comes with N.ema.model, the averaged generators"""
+    assert mode in ["train", "interp", "gen"]
+    model = make_model('test1_nobn_bilin_both_ema', **kw.pop('backend', {}))
+    if mode == "train":
+        _train(model, "test1_nobn_bilin_both_ema", num_epochs, **kw)
+    return model
+
+
 def main(argv):
     fn = {'test1_nobn': test1_nobn, 'test1_nobn_finetunep2p_bilin': test1_nobn_finetunep2p_bilin,
-          'test1_nobn_bilin_both': test1_nobn_bilin_both, 'test1_nobn_bilin_both_pixeld': test1_nobn_bilin_both_pixeld}[argv[1]]
+          'test1_nobn_bilin_both': test1_nobn_bilin_both, 'test1_nobn_bilin_both_pixeld': test1_nobn_bilin_both_pixeld,
+          'test1_nobn_bilin_both_ema': test1_nobn_bilin_both_ema}[argv[1]]
     fn(argv[2])
 
 

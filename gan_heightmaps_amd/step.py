@@ -23,7 +23,7 @@ from . import layers as L
 from .device import Ops
 from .engine import NetPlan, ParamStore
 from .input_pipeline import InputPipeline
-from .step_build import LANE_OF, StepBuilder
+from .step_build import EMA_NETS, LANE_OF, StepBuilder
 
 TRAIN_KEYS = ['dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_recon', 'p2p_disc']
 
@@ -90,11 +90,36 @@ def _interleave(a, b):
     return out
 
 
+class _EmaWeights:
+    """the context manager GanStep.ema_weights() returns"""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def __enter__(self):
+        eng = self.eng
+        eng._live_only("ema_weights")       # (nested entry)
+        eng._swap_ema()
+        eng._in_ema = True
+        return eng
+
+    def __exit__(self, *exc):
+        self.eng._in_ema = False
+        self.eng._swap_ema()
+        return False
+
+
 class GanStep:
     def __init__(self, dev, dcgan_gen, dcgan_disc, p2p_gen, p2p_disc, alpha, lsgan, reconstruction, opt_spec,
                  train_mode='both', comm=None, use_graph=True, two_streams=True, force_exchange=False,
-                 side_streams=None, dtype='bf16x3', bucket_mb=None, exchange_mode=None):
+                 side_streams=None, dtype='bf16x3', bucket_mb=None, exchange_mode=None, ema=None):
         self.dev = dev
+        # exponential moving average of the two generators' parameters, kept on the device behind every update (DESIGN
+        # §4o): the decay in [0, 1), or None = no average, nothing allocated, the step's program as it always was
+        if ema is not None and not (0.0 <= float(np.float32(ema)) < 1.0):
+            raise ValueError("ema must be a decay in [0, 1) or None, not %r" % (ema,))
+        self.ema = None if ema is None else float(ema)         # (the kernel takes it rounded to fp32)
+        self._in_ema = False                # inside ema_weights(): w and ema are exchanged
         # form of the data-parallel exchange: 'allreduce' (SURVEY 8e: every rank sums every gradient and runs the whole
         # optimiser), 'allreduce_bf16' (the same program with every gradient sub-bucket rounded to bf16 for the trip: half the
         # bytes on the xGMI links, a REDUCED-PRECISION exchange, opt-in; for the first multi-GPU node to A/B) or 'rs_ag'
@@ -151,6 +176,10 @@ class GanStep:
             st.opt_state = {name: d.zeros((1, st.n_pad, 1, 1)) for name in self.opt_rule.slots}
         if hasattr(opt_spec.learning_rate, '_listeners'):
             opt_spec.learning_rate._listeners.append(self.set_lr)
+        if self.ema is not None:
+            for k in EMA_NETS:              # n_pad floats on the net's own lane, zeroed; the average starts at the weights
+                self.stores[k].ema = self.devs[LANE_OF[k]].zeros((1, self.stores[k].n_pad, 1, 1))
+            self._copy_w_to_ema(EMA_NETS)
         self.losses_dev = dev.zeros((1, 8, 1, 1))
         self._built = {}                    # {B or (B, slot): the plan set} (step_build.py)
         self._infer = {}
@@ -205,12 +234,16 @@ class GanStep:
         if self.sharded and self.dtype == 'f16':
             raise NotImplementedError("exchange_mode='rs_ag' with the fp16 dynamic loss scale: every rank would check only its "
                                       "own gradient shard for overflow; use bf16 (no scale) or the all-reduce form")
+        if self.sharded and self.ema is not None:
+            raise NotImplementedError("exchange_mode='rs_ag' with ema: the sharded update runs on 1 / world of the parameters "
+                                      "per rank, so the average would have to become a sharded slot; use the all-reduce form")
         self.shard_unit = 64 * self.world if self.sharded else 1       # elements: world shards of whole 256-byte lines
 
     @property
     def param_version(self):
         """moves whenever parameters or BatchNorm running statistics may have changed on the device: every train / loss /
-        non-deterministic forward call issued and every host write to a parameter (world.py keys its chunk cache on it)"""
+        non-deterministic forward call issued, every host write to a parameter and both edges of ema_weights() (world.py
+        keys its chunk cache on it)"""
         return self._param_ticks + sum(st.version for st in self.stores.values())
 
     def loss_scale_state(self):
@@ -260,12 +293,15 @@ class GanStep:
         zero: exact, and it needs no further collective in the C ABI."""
         if self.comm is None or self.world == 1:
             return
+        self._live_only("broadcast_parameters")
         self._param_ticks += 1
         self.sync()
         for k in ('dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_disc'):
             st = self.stores[k]
             bufs = [(st.w, st.n_train), (st.s, st.n_state)] + [(t, st.n_train) for _, t in sorted(st.opt_state.items())]
             bufs.append((self.hyper[k], 2))
+            if self.ema is not None and k in EMA_NETS:
+                bufs.append((st.ema, st.n_train))
             for t, n in bufs:
                 if n <= 0:
                     continue
@@ -281,9 +317,64 @@ class GanStep:
         crc = 0
         for k in ('dcgan_gen', 'dcgan_disc', 'p2p_gen', 'p2p_disc'):
             st = self.stores[k]
-            for t in (st.w, st.s):
+            for t in (st.w, st.s) + ((st.ema,) if self.ema is not None and k in EMA_NETS else ()):
                 crc = zlib.crc32(t.numpy().tobytes(), crc)
         return crc_range(self.comm if self.world > 1 else None, crc)
+
+    # ---- the exponential moving average of the generators ----------------------------------------
+    def _live_only(self, what):
+        """inside ema_weights() the parameter buffers hold the average: whatever would move parameters or state is refused"""
+        if self._in_ema:
+            raise RuntimeError("%s inside ema_weights(): the parameter buffers hold the averaged weights until the block ends"
+                               % what)
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise ValueError("%s: this model keeps no average (construct it with ema=<decay>)" % what)
+
+    def _copy_w_to_ema(self, keys):
+        for k in keys:
+            st = self.stores[k]
+            if st.n_train:
+                st.dev.d2d(st.ema.ptr, st.w.ptr, 4 * st.n_train)
+
+    def reset_ema(self, keys=EMA_NETS):
+        """start the average again from the current weights (after a warm-up; load_model does it for the nets it loads)"""
+        self._need_ema("reset_ema")
+        self._live_only("reset_ema")
+        self.close_pipeline()
+        self.sync()
+        self._copy_w_to_ema([k for k in keys if k in EMA_NETS])
+        self.sync()
+
+    def _swap_ema(self):
+        self.close_pipeline()
+        self.sync()
+        for k in EMA_NETS:
+            st = self.stores[k]
+            self.ops[LANE_OF[k]].swap_f32(st.w, st.ema, st.n_train)
+        self._param_ticks += 1          # param_version: TerrainWorld drops its chunk and head caches
+        self.sync()
+
+    def ema_weights(self):
+        """``with eng.ema_weights(): ...`` -- inside the block the generators' parameter buffers hold the averaged weights
+        (exchanged with the average on the device, and exchanged back on exit, also when the body raises), so everything
+        that reads parameters -- the deterministic forwards, generate_chain, texture_heightmap, generate_terrain,
+        terrain_world, get_all_param_values, save_model -- sees them with no further change; BatchNorm running statistics
+        stay the live ones.  Whatever would move parameters or state raises RuntimeError inside."""
+        self._need_ema("ema_weights")
+        self._live_only("ema_weights")
+        return _EmaWeights(self)
+
+    def ema_values(self, key):
+        """get_all_param_values of generator ``key`` with the averaged values in place of the trainable ones (read from the
+        average's buffer: nothing is exchanged, param_version does not move)"""
+        self._need_ema("ema_values")
+        self.sync()
+        st = self.stores[key]
+        src = st.w if self._in_ema else st.ema          # inside ema_weights() the parameter buffer IS the average
+        return [st._from_device_layout(p, st._view(src, p).numpy().ravel()) if p.index[0] == 'w' else st.download(p)
+                for p in st.params]
 
     def set_lr(self, lr):
         self.sync()
@@ -294,7 +385,7 @@ class GanStep:
 
     # ---- training state (checkpoint / resume) ------------------------------------------------------------
     # Everything a step reads besides the parameters and the batch: per net the optimiser slots and hyper = [lr, t], the
-    # dropout step counters and the fp16 loss-scale records.  Restored IN PLACE: recorded programs and captured graphs hold
+    # dropout step counters and the fp16 loss-scale records; with GanStep(ema=decay) the decay and the generators' averages.  Restored IN PLACE: recorded programs and captured graphs hold
     # these buffers' pointers.
     def _counters(self):
         """{(name, batch size): DevTensor} of every dropout counter that exists: the train plans' per (net, B) ('G' / 'U'),
@@ -323,6 +414,7 @@ class GanStep:
         stream first.  Sharded update (rs_ag): a rank's optimiser slots are current on its own shards only -- they are
         all-gathered bucket by bucket first (a collective: every rank calls this), so the state is that of the whole net,
         whatever the world size.  Otherwise the state is replicated and this rank's copy is it."""
+        self._live_only("training_state")
         self.close_pipeline()
         self.sync()
         if self.sharded and self.opt_rule.slots:
@@ -341,6 +433,10 @@ class GanStep:
                 'n_train': st.n_train, 'n_state': st.n_state,
                 'hyper': self.hyper[k].numpy().ravel()[:2].copy(),
                 'slots': {s: st.opt_state[s].numpy().ravel()[:st.n_train].copy() for s in self.opt_rule.slots}}
+            if self.ema is not None and k in EMA_NETS:
+                state['nets'][k]['ema'] = st.ema.numpy().ravel()[:st.n_train].copy()
+        if self.ema is not None:
+            state['ema'] = self.ema
         counters = {k: int(t.numpy().ravel()[:1].view(np.uint32)[0]) for k, t in self._counters().items()}
         counters.update(self._pending_counters or {})       # restored, plan not built since
         state['rng_counters'] = counters
@@ -365,11 +461,24 @@ class GanStep:
         if len(state.get('loss_scale', [])) != len(self._ls_state):
             raise ValueError("training state: %d loss-scale records in the checkpoint, %d in this run"
                              % (len(state.get('loss_scale', [])), len(self._ls_state)))
+        ck = state.get('ema')
+        if ck is not None and (self.ema is None or float(ck) != self.ema):
+            raise ValueError("training state: ema is %r in the checkpoint, %r in this run" % (ck, self.ema))
+        if ck is not None:
+            for k in EMA_NETS:
+                if np.asarray(state['nets'][k].get('ema', ())).size != self.stores[k].n_train:
+                    raise ValueError("training state: the ema values of %s do not fit this run" % k)
+        elif self.ema is not None:
+            import warnings
+            warnings.warn("training state: the checkpoint carries no ema; the averages restart from the loaded weights",
+                          RuntimeWarning)
 
     def restore_training_state(self, state):
         """inverse of training_state, into the existing buffers.  Every rank loads whole buffers (in the sharded form each
         then updates its own shards, as before); padding is zeroed; dropout counters of plans not built yet are applied
-        when they are built, counters the checkpoint does not know restart at zero."""
+        when they are built, counters the checkpoint does not know restart at zero.  The generators' averages (ema) are
+        written in place too; from a checkpoint without them they restart from the weights already loaded."""
+        self._live_only("restore_training_state")
         self.check_training_state(state)
         self.close_pipeline()
         self.sync()
@@ -380,6 +489,13 @@ class GanStep:
                 full[:st.n_train] = np.asarray(sv['slots'][s], np.float32)
                 st.opt_state[s].set(full)
             self.hyper[k].set(np.asarray(sv['hyper'], np.float32))
+            if self.ema is not None and k in EMA_NETS:
+                full = np.zeros(st.n_pad, np.float32)
+                if state.get('ema') is not None:
+                    full[:st.n_train] = np.asarray(sv['ema'], np.float32)
+                st.ema.set(full)
+                if state.get('ema') is None:        # a checkpoint without an average: it restarts from the loaded weights
+                    self._copy_w_to_ema([k])
         self._pending_counters = dict(state['rng_counters'])
         for key, t in self._counters().items():
             t.set(np.asarray([self._pending_counters.pop(key, 0)], np.uint32).view(np.float32))
@@ -442,9 +558,11 @@ class GanStep:
         self.pipeline.enqueue_train_uploaded(b, wrap)
 
     def train_pipelined(self, batches):
+        self._live_only("train_pipelined")
         return self.pipeline.train_pipelined(batches)
 
     def train_pipelined_from_iterator(self, it, Z_sampler, steps):
+        self._live_only("train_pipelined_from_iterator")
         return self.pipeline.train_pipelined_from_iterator(it, Z_sampler, steps)
 
     def close_pipeline(self):
@@ -516,6 +634,7 @@ class GanStep:
         return [np.float32(x) for x in v]
 
     def train(self, Z, X, Y, read_losses=True):
+        self._live_only("train")
         b = self.built(int(np.shape(X)[0]))
         self._upload(b, Z, X, Y)
         self.enqueue_train(b)
@@ -524,6 +643,7 @@ class GanStep:
     def run_from_iterator(self, it, Z_sampler, train=True):
         """One train_fn / loss_fn call whose (A, B) batch is produced on the device by a data.Hdf5Iterator
         (uint8 upload + ghm_image_batch straight into the step's input buffers; no fp32 host batch)."""
+        self._live_only("run_from_iterator")
         n = it.peek_n()
         b = self.built(n)
         self.sync()
@@ -537,6 +657,7 @@ class GanStep:
         return self._read_losses()
 
     def _run_loss(self, b):
+        self._live_only("loss")
         self._param_ticks += 1                  # loss_fn still updates the BatchNorm running statistics
         if self.use_graph == 'recorded':
             self._run_recorded(b, 'loss')
@@ -592,6 +713,7 @@ class GanStep:
 
     def enqueue_train(self, b, wrap=None):
         """one train step on the data already resident in b.z / b.x / b.y (asynchronous)"""
+        self._live_only("train")
         self._param_ticks += 1
         if self.use_graph == 'recorded':
             return self._run_recorded(b, 'train', wrap)
@@ -610,6 +732,7 @@ class GanStep:
         self.cops.allreduce_sum(self.losses_dev, 8)
 
     def loss(self, Z, X, Y):
+        self._live_only("loss")
         b = self.built(int(np.shape(X)[0]))
         self._upload(b, Z, X, Y)
         self._run_loss(b)
@@ -618,6 +741,7 @@ class GanStep:
     def profile_train(self, B):
         """[(label, ms, meta)] per program entry, stream by stream (synchronising; mutates parameters like a
         real step: compute, then the exchange, then the updates)."""
+        self._live_only("profile_train")
         self._param_ticks += 1
         b = self.built(B)
         out = []
@@ -670,6 +794,8 @@ class GanStep:
         return self._subgraph[k]
 
     def generate(self, key, inp, deterministic=False):
+        if not deterministic:
+            self._live_only("a non-deterministic forward (it moves the BatchNorm running statistics)")
         inp = np.ascontiguousarray(inp, np.float32)
         plan, prog = self._infer_plan(key, inp.shape[0], deterministic)
         self._param_ticks += not deterministic  # batch statistics move the running ones
@@ -682,6 +808,8 @@ class GanStep:
     def generate_chain(self, Z, deterministic=True):
         """z -> G(z) -> U(G(z)) without leaving HBM (the z_fn -> gen_fn chain of generate_interpolation_clip,
         /root/reference/pix2pix.py:384-393).  Returns (heightmaps, textures) as numpy arrays."""
+        if not deterministic:
+            self._live_only("a non-deterministic forward (it moves the BatchNorm running statistics)")
         Z = np.ascontiguousarray(Z, np.float32)
         pg, prog_g = self._infer_plan('dcgan_gen', Z.shape[0], deterministic)
         pu, prog_u = self._infer_plan('p2p_gen', Z.shape[0], deterministic)

@@ -9,6 +9,7 @@ from . import layers as L
 from .engine import NetPlan
 
 LANE_OF = {'dcgan_gen': 0, 'dcgan_disc': 0, 'p2p_gen': 1, 'p2p_disc': 1}
+EMA_NETS = ('dcgan_gen', 'p2p_gen')        # the nets inference runs: only they keep an average (GanStep(ema=decay))
 
 
 def _has_bn(layer):
@@ -393,6 +394,10 @@ class StepBuilder:
                 o, st.w, st.g, sv, st.n_train, hy, hp, gs)))
             if rule.ticks:
                 b.update[lane].append((kind + "_tick_" + k, lambda hy=hy, o=o: o.adam_tick(hy)))
+            if eng.ema is not None and k in EMA_NETS:
+                # the generator's average follows its update on the same stream; in fp16 it reads the same
+                # overflow flag, so it stands before loss_scale_update clears it
+                b.update[lane].append(("ema_" + k, lambda st=st, o=o: o.ema_update(st.ema, st.w, st.n_train, eng.ema)))
         if eng._ls_state:
             for lane in (0, 1):
                 if b.update[lane]:
