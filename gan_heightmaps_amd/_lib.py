@@ -29,6 +29,12 @@ class RenderParams(C.Structure):
                 ("horizon", C.c_float * 3), ("zenith", C.c_float * 3), ("accel", C.c_int32), ("out_u8", C.c_int32)]
 
 
+class ErosionParams(C.Structure):
+    """ghm_erosion_params"""
+    _fields_ = [(k, C.c_float) for k in ("dt", "rain", "evaporation", "gravity", "pipe", "capacity", "dissolve", "deposit",
+                                         "min_tilt", "max_speed", "min_depth", "height_scale")]
+
+
 _p, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _D = C.POINTER(ConvDesc)
 
@@ -182,6 +188,9 @@ SIGNATURES = {
     "ghm_world_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_render_maxmip": [_p, _p, _i32, _i32, _p, _i64],
     "ghm_render_view": [_p, C.POINTER(RenderParams), _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],
+    "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
+    "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
+    "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
     "ghm_lsgan_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_bce_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_recon_loss": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _f, _i32],
@@ -220,7 +229,8 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_split_pool_supported": ([_D, _i32], C.c_int),
             "ghm_split_q_direct": ([_D, _i32], C.c_int),
             "ghm_split_dgrad_dact_supported": ([_D], C.c_int),
-            "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64)}
+            "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64),
+            "ghm_erosion_tile": ([_i32], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)
 
 _lib = None

@@ -420,6 +420,19 @@ def render_params(pos, yaw, pitch, fov, size, height_scale, step, max_dist, sun_
     return p
 
 
+EROSION_PLANES = 7                 # GHM_EROSION_PLANES (include/ghm.h): b, d, s, fL, fR, fT, fB
+
+
+def erosion_params(**kw):
+    """a ghm_erosion_params (include/ghm.h) from its twelve fields by name"""
+    p = _lib.ErosionParams()
+    for k, _ in p._fields_:
+        setattr(p, k, float(kw.pop(k)))
+    if kw:
+        raise TypeError("unknown erosion parameters: %s" % sorted(kw))
+    return p
+
+
 def _vp(x):
     if x is None:
         return C.c_void_p(0)
@@ -1128,6 +1141,33 @@ class Ops:
         call("ghm_render_view", self.h, C.byref(params) if params is not None else None, _vp(hm_ptr), _vp(tex_ptr), int(H),
              int(W), _vp(mip.ptr if mip is not None else None), mip.H if mip is not None else 0,
              mip.W if mip is not None else 0, _vp(out_ptr), _vp(depth_ptr))
+
+    # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
+    @staticmethod
+    def erosion_tile():
+        """(rows, columns) of the fused form's tile"""
+        lib = _lib.load()
+        return int(lib.ghm_erosion_tile(0)), int(lib.ghm_erosion_tile(1))
+
+    def erosion_init(self, hm_ptr, H, W, src_pitch, height_scale, state_ptr, pitch):
+        """the fp32 heightmap at hm_ptr (H rows of src_pitch cells, in [0, 1]) -> the state at state_ptr: EROSION_PLANES
+        planes of H rows of ``pitch`` cells, b = heightmap * height_scale, the rest 0"""
+        call("ghm_erosion_init", self.h, _vp(hm_ptr), int(H), int(W), int(src_pitch), float(height_scale), _vp(state_ptr),
+             int(pitch))
+
+    def erosion_iterate(self, params, state0, state1, tmp, H, W, pitch, iterations, fused):
+        """``iterations`` steps from state0, alternating between the two states -> the pointer of the state that holds the
+        result.  params: an ErosionParams (erosion_params()); tmp: three planes, needed by the plain form only"""
+        call("ghm_erosion_iterate", self.h, C.byref(params) if params is not None else None, _vp(state0), _vp(state1),
+             _vp(tmp), int(H), int(W), int(pitch), int(iterations), int(bool(fused)))
+        return state0 if iterations % 2 == 0 else state1
+
+    def erosion_emit(self, state_ptr, H, W, pitch, height_scale, r0, c0, nr, nc, out_u8, out_ptr, out_rows, out_pitch,
+                     yoff=0, xoff=0):
+        """clamp(b / height_scale, 0, 1) of rows [r0, r0 + nr) x columns [c0, c0 + nc) of the state -> rows yoff ..,
+        columns xoff .. of the plane at out_ptr (out_rows rows of out_pitch cells), fp32 or uint8"""
+        call("ghm_erosion_emit", self.h, _vp(state_ptr), int(H), int(W), int(pitch), float(height_scale), int(r0), int(c0),
+             int(nr), int(nc), int(bool(out_u8)), _vp(out_ptr), int(out_rows), int(out_pitch), int(yoff), int(xoff))
 
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous

@@ -159,10 +159,22 @@ class Pix2Pix:
         (gan_heightmaps_amd/world.py).  Not in the reference.
         kw: chunk_cells (default: a fixed memory budget; part of the world's identity), blend ('bilinear' | 'mosaic'),
         overlap (texture tiles, default in_shp / 4), batch_size (tiles per pass), cache_mb, latent_fn(i, j) -> [latent_dim]
-        in place of the seeded sampler draw.  Use it as a context manager, or close() it.  Leaves the training state
-        untouched."""
+        in place of the seeded sampler draw, erosion (an erosion.Erosion: the world is then the eroded one, every chunk
+        eroded over a window with an exact halo).  Use it as a context manager, or close() it.  Leaves the
+        training state untouched."""
         from .world import TerrainWorld
         return TerrainWorld(self, seed, **kw)
+
+    def erode_heightmap(self, heightmap, erosion=None, **kw):
+        """Erode a heightmap with a pipe-model water simulation on the GPU (gan_heightmaps_amd/erosion.py).  Not
+        in the reference.  heightmap: (H, W) or (1, H, W), floating point in [0, 1] (what a greyscale generator returns) or
+        uint8; the array's edge is a wall.  erosion: an erosion.Erosion (default Erosion()); kw: erode's (fused, water,
+        out, uint8).  Returns the eroded heightmap in the input's shape, float32 in [0, 1].  Leaves the training state
+        untouched."""
+        from .erosion import erode
+        from .step import LANE_OF
+        self.engine.sync()
+        return erode(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, erosion, **kw)
 
     def render_terrain(self, heightmap, texture, camera, height_scale=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),

@@ -13,7 +13,7 @@ unbounded world (the scene is assembled through the host: ``both`` -> upload; ``
 ``TerrainWorld.flight`` assemble it on the device from the resident chunks).
 
     python -m gan_heightmaps_amd.render OUT.png (--heightmap F --texture F | --world EXPERIMENT MODEL --seed N
-        [--chunk-cells C] [--blend B] [--dtype D]) --pos Y,X,Z (--look-at Y,X,Z | --yaw A --pitch A) [--fov DEG]
+        [--chunk-cells C] [--blend B] [--dtype D] [--erode N]) --pos Y,X,Z (--look-at Y,X,Z | --yaw A --pitch A) [--fov DEG]
         [--size HxW] [--max-dist N] [--height-scale S] [--sun AZ,EL] [--no-shadows] [--haze V] [--step V]
         [--frames N --to Y,X,Z [--window-mb M]]
 """
@@ -361,6 +361,8 @@ def parse_args(argv):
     p.add_argument("--blend", default=None, choices=["mosaic", "bilinear"], help="how cells meet (with --world)")
     p.add_argument("--dtype", default=None, choices=["f32", "bf16x3", "bf16x2", "bf16", "f16"],
                    help="arithmetic of the convolutions (with --world; default bf16x3)")
+    p.add_argument("--erode", type=int, default=None, metavar="N",
+                   help="erode the world with N iterations of the water simulation (with --world)")
     p.add_argument("--pos", type=_triple, required=True, metavar="Y,X,Z", help="the camera's position")
     p.add_argument("--look-at", type=_triple, default=None, metavar="Y,X,Z", help="a point on the camera's axis")
     p.add_argument("--yaw", type=float, default=None, help="degrees; 0 faces down the rows, 90 along the columns")
@@ -398,8 +400,11 @@ def parse_args(argv):
             p.error("--world needs --max-dist: an unbounded world has no farthest corner")
         if a.chunk_cells is not None and a.chunk_cells < 1:
             p.error("--chunk-cells must be >= 1")
-    elif a.seed is not None or a.chunk_cells is not None or a.blend is not None or a.dtype is not None:
-        p.error("--seed / --chunk-cells / --blend / --dtype need --world")
+        if a.erode is not None and a.erode < 1:
+            p.error("--erode must be >= 1")
+    elif a.seed is not None or a.chunk_cells is not None or a.blend is not None or a.dtype is not None \
+            or a.erode is not None:
+        p.error("--seed / --chunk-cells / --blend / --dtype / --erode need --world")
     if (a.look_at is not None) == (a.yaw is not None or a.pitch is not None):
         p.error("give either --look-at, or --yaw and --pitch")
     if a.look_at is None and (a.yaw is None or a.pitch is None):
@@ -470,6 +475,9 @@ def main(argv=None):
             model = make_model(a.world[0], dtype=a.dtype or "bf16x3", verbose=False)
             model.load_model(a.world[1], mode='both')
             wkw = {k: v for k, v in (("chunk_cells", a.chunk_cells), ("blend", a.blend)) if v is not None}
+            if a.erode is not None:
+                from .erosion import Erosion
+                wkw["erosion"] = Erosion(iterations=a.erode)
             world = model.terrain_world(a.seed, **wkw)
             if a.window_mb is not None:
                 # a window after the other, each built on the device: memory does not grow with the path

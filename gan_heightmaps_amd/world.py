@@ -25,8 +25,14 @@ Rendering: ``scene`` hands a rectangle to the ray caster -- 
 assembled on the device by sinks that write a render.Scene's planes --, and ``flight`` renders a camera path of any length
 from one bounded scene window after the other (``flight_plan``: the window rule).
 
+Erosion: with ``erosion=`` the world IS the eroded one.  What ``_compute`` makes becomes a raw layer; chunk
+(a, b) of ``_chunks`` is erosion.erode's simulation over the raw rectangle [aK - E, (a+1)K + E)^2, E = erosion.halo, gathered
+on the device from the at most nine raw chunks it touches, with the centre K x K emitted into the chunk buffer.  The window does
+not depend on the request and a cell E from every wall does not feel it, so requests still agree bit for bit; everything
+downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the eroded chunks through the code it has.
+
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
-        [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]]
+        [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
 """
 import argparse
 import re
@@ -35,13 +41,15 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import erosion as _erosion
 from . import layers as L
 from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
 from . import terrain as _terrain
 from .texture import check_overlap
 
 __all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
-           "window_elements", "default_chunk_cells", "slot_batches", "snap_out", "plan_windows", "TerrainWorld", "parse_region",
+           "window_elements", "default_chunk_cells", "slot_batches", "erosion_sources", "snap_out", "plan_windows", "TerrainWorld",
+           "parse_region",
            "parse_args", "main"]
 
 HEAD_BLOCK = 8                   # the head runs over world-aligned blocks of HEAD_BLOCK x HEAD_BLOCK cells, one pass each
@@ -107,6 +115,21 @@ def slot_batches(q_lo, q_hi, B):
     for k in range(q_lo // B, q_hi // B + 1):
         lo, hi = max(B * k, q_lo), min(B * k + B - 1, q_hi)
         out.append(([min(max(B * k + j, q_lo), q_hi) for j in range(B)], lo - B * k, hi - lo + 1))
+    return out
+
+
+def erosion_sources(a, b, K, E):
+    """what the eroded chunk (a, b) is made from: the raw chunks that the window [aK - E, (a+1)K + E)^2 touches, row-major,
+    as [((ra, rb), r0, c0, nr, nc, wy, wx)] -- rows [r0, r0 + nr) x columns [c0, c0 + nc) of raw chunk (ra, rb) go to rows
+    wy .., columns wx .. of the window.  With 0 < E <= K these are the nine chunks around (a, b), negative indices included."""
+    y0, x0, n = a * K - E, b * K - E, K + 2 * E
+    (a_lo, a_hi), (b_lo, b_hi) = axis_chunks(y0, n, K), axis_chunks(x0, n, K)
+    out = []
+    for ra in range(a_lo, a_hi + 1):
+        ya, yb = max(y0, ra * K), min(y0 + n, (ra + 1) * K)
+        for rb in range(b_lo, b_hi + 1):
+            xa, xb = max(x0, rb * K), min(x0 + n, (rb + 1) * K)
+            out.append(((ra, rb), ya - ra * K, xa - rb * K, yb - ya, xb - xa, ya - y0, xa - x0))
     return out
 
 
@@ -317,7 +340,7 @@ class TerrainWorld:
     """An unbounded terrain addressed by pixel coordinates.  See Pix2Pix.terrain_world and the module docstring."""
 
     def __init__(self, model, seed, chunk_cells=None, blend='bilinear', overlap=None, batch_size=4, cache_mb=1024,
-                 latent_fn=None, deterministic=True, verbose=False):
+                 latent_fn=None, deterministic=True, verbose=False, erosion=None):
         if not deterministic:
             raise NotImplementedError("terrain_world needs deterministic=True: with batch statistics a pixel would depend "
                                       "on what shares its pass, not on (weights, seed, coordinates) alone")
@@ -352,10 +375,28 @@ class TerrainWorld:
         self._heads = OrderedDict()                               # (I, J) -> DevTensor [HEAD_BLOCK^2, nch s s]
         self._pool, self._pinned, self._table = [], set(), None
         self._version, self._closed = None, False
-        self.computed = 0                                         # chunks computed so far (a cache hit computes nothing)
+        self.computed = 0                                         # raw chunks computed so far (a cache hit computes nothing)
+        # ---- the eroded layer: _chunks holds eroded chunks, _raw what _compute makes; one LRU over both ----
+        if erosion is not None:
+            if not isinstance(erosion, _erosion.Erosion):
+                raise ValueError("erosion must be an erosion.Erosion, got %r" % (erosion,))
+            if geo.channels != 1:
+                raise ValueError("erosion needs one height per pixel, this generator has %d channels" % geo.channels)
+            if erosion.halo > self._K:
+                raise ValueError("erosion: %d iterations reach %d pixels, more than a chunk of %d: a window would read "
+                                 "beyond the nine chunks around its own; raise chunk_cells or lower iterations"
+                                 % (erosion.iterations, erosion.halo, self._K))
+            n = self._K + 2 * erosion.halo
+            if n * n >= INT32_LIMIT or n > 4 * 65535:
+                raise ValueError("erosion: a window of %d x %d cells is beyond the kernels' range" % (n, n))
+        self.erosion = erosion
+        self.eroded = 0                                           # erosions run so far
+        self._raw, self._stamp, self._tick = OrderedDict(), {}, 0
+        self._ero, self._fused = None, _erosion.DEFAULT_FUSED     # one window's states, allocated once; the kernels' form
         if verbose:
-            print("terrain_world: seed %d, chunk_cells %d (%d px), blend %s, overlap %d"
-                  % (self.seed, self._c, self._K, blend, self.overlap))
+            print("terrain_world: seed %d, chunk_cells %d (%d px), blend %s, overlap %d%s"
+                  % (self.seed, self._c, self._K, blend, self.overlap,
+                     "" if erosion is None else ", eroded %d iterations" % erosion.iterations))
 
     chunk_cells = property(lambda self: self._c)
     chunk_px = property(lambda self: self._K)
@@ -403,9 +444,11 @@ class TerrainWorld:
             self._version = eng.param_version
 
     def _drop(self):
-        for p in self._chunks.values():
+        for p in list(self._chunks.values()) + list(self._raw.values()):
             self._pool.append(p)
         self._chunks.clear()
+        self._raw.clear()
+        self._stamp.clear()
         for t in self._heads.values():
             self._dev.free(t.ptr)
         self._heads.clear()
@@ -465,8 +508,75 @@ class TerrainWorld:
         self.computed += 1
         return ptr
 
+    # ---- the eroded layer ---------------------------------------------------------------------------------------------
+    def _touch(self, layer, key):
+        self._tick += 1
+        self._stamp[(layer, key)] = self._tick
+
+    def _evict_layers(self, keep, size):
+        """one LRU over raw ('r') and eroded ('e') chunks: the least recently used outside ``keep`` go until ``size`` fits"""
+        cap = self._capacity()
+        if size <= cap:
+            return
+        for _, (layer, k) in sorted((t, lk) for lk, t in self._stamp.items() if lk not in keep):
+            if size <= cap:
+                break
+            self._pool.append((self._chunks if layer == 'e' else self._raw).pop(k))
+            del self._stamp[(layer, k)]
+            size -= 1
+
+    def _erode(self, srcs):
+        """the window of one chunk: gathered from its resident raw chunks, eroded, its centre K x K -> a chunk buffer"""
+        ero, K, dev, ops = self.erosion, self._K, self._dev, self._ops
+        E = ero.halo
+        n = K + 2 * E
+        plane = 4 * n * n
+        if self._ero is None:
+            from .device import erosion_params
+            self._ero = dev.alloc(_erosion.workspace_planes(self._fused) * plane)
+            self._ero_params = erosion_params(**ero.as_dict())
+        s0, s1 = self._ero, self._ero + _erosion.PLANES * plane
+        tmp = None if self._fused else s1 + _erosion.PLANES * plane
+        # the raw window lands in the second state's first plane, which nothing reads before the first step writes it
+        for key, r0, c0, nr, nc, wy, wx in srcs:
+            ops.world_crop(self._raw[key], 1, K, r0, c0, nr, nc, False, True, s1 + 4 * wy * n, n, wx)
+        ops.erosion_init(s1, n, n, n, ero.height_scale, s0, n)
+        fin = ops.erosion_iterate(self._ero_params, s0, s1, tmp, n, n, n, ero.iterations, self._fused)
+        ptr = self._pool.pop() if self._pool else dev.alloc(self._chunk_bytes)
+        ops.erosion_emit(fin, n, n, n, ero.height_scale, E, E, K, K, False, ptr, K, K)
+        self.eroded += 1
+        return ptr
+
+    def _acquire_eroded(self, keys):
+        missing = [k for k in keys if k not in self._chunks]
+        if missing and self._udev is not self._dev:
+            self._dev.wait_for(self._udev)
+        keep = {('e', k) for k in set(keys) | self._pinned}
+        resident = lambda: len(self._chunks) + len(self._raw)
+        for k in keys:
+            if k in self._chunks:
+                self._touch('e', k)
+                continue
+            srcs = erosion_sources(k[0], k[1], self._K, self.erosion.halo)
+            need = keep | {('r', s[0]) for s in srcs}
+            for s in srcs:
+                if s[0] not in self._raw:
+                    self._evict_layers(need, resident() + 1)
+                    self._raw[s[0]] = self._compute(*s[0])
+                self._touch('r', s[0])
+            self._evict_layers(need, resident() + 1)
+            self._chunks[k] = self._erode(srcs)
+            self._touch('e', k)
+        self._pinned = set(keys)
+        self._evict_layers({('e', k) for k in keys}, resident())
+        self._trim_heads(4 * HEAD_BLOCK if self._capacity() else 0)
+        if missing and self._udev is not self._dev:
+            self._udev.wait_for(self._dev)
+
     def _acquire(self, keys):
         """make the chunks ``keys`` resident (they stay so until the next _acquire), then evict down to the budget"""
+        if self.erosion is not None:
+            return self._acquire_eroded(keys)
         missing = [k for k in keys if k not in self._chunks]
         if missing and self._udev is not self._dev:
             self._dev.wait_for(self._udev)                        # a recycled buffer may still feed an earlier gather
@@ -484,6 +594,8 @@ class TerrainWorld:
             self._udev.wait_for(self._dev)
 
     def _evict(self, keep, size):
+        if self.erosion is not None:
+            return self._evict_layers({('e', k) for k in keep}, size + len(self._raw))
         cap = self._capacity()
         for k in [k for k in self._chunks if k not in keep]:
             if size <= cap:
@@ -520,6 +632,9 @@ class TerrainWorld:
         if self._table is not None:
             self._dev.free(self._table.ptr)
             self._table = None
+        if self._ero is not None:
+            self._dev.free(self._ero)
+            self._ero = None
 
     # ---- requests -------------------------------------------------------------------------------------------------------
     def _check_region(self, y0, x0, h, w):
@@ -774,6 +889,9 @@ def parse_args(argv):
                    help="also texture the region with the pix2pix generator: .png, or .npy (uint8 (H, W, 3))")
     p.add_argument("--overlap", type=int, default=None, help="texture tile overlap in pixels (default in_shp / 4)")
     p.add_argument("--batch-size", type=int, default=4, help="texture tiles per forward pass (default 4)")
+    p.add_argument("--erode", type=int, default=None, metavar="N",
+                   help="erode the world with N iterations of the water simulation (erosion.Erosion's other defaults); "
+                        "part of the world's identity")
     # a region that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i, tok in enumerate(argv[:-1]):
@@ -789,6 +907,8 @@ def parse_args(argv):
         p.error("--overlap must be >= 0")
     if a.texture is None and (a.overlap is not None or a.batch_size != 4):
         p.error("--overlap / --batch-size need --texture")
+    if a.erode is not None and a.erode < 1:
+        p.error("--erode must be >= 1")
     return a
 
 
@@ -800,8 +920,9 @@ def main(argv=None):
     model = make_model(a.experiment, dtype=a.dtype, verbose=False)
     model.load_model(a.model, mode='both' if a.texture else 'dcgan')
     y0, x0, h, w = a.region
+    wkw = {} if a.erode is None else {"erosion": _erosion.Erosion(iterations=a.erode)}
     with model.terrain_world(a.seed, chunk_cells=a.chunk_cells, blend=a.blend, overlap=a.overlap,
-                             batch_size=a.batch_size, verbose=True) as world:
+                             batch_size=a.batch_size, verbose=True, **wkw) as world:
         C = world.geometry.channels
         hm = np.lib.format.open_memmap(a.output, mode="w+", dtype=np.float32, shape=(C, h, w)) \
             if a.output.endswith(".npy") else None
