@@ -191,6 +191,12 @@ SIGNATURES = {
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
+    "ghm_swd_pyramid_level": [_p, _p, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _p, _i32, _p, _i32],
+    "ghm_swd_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _i64, _i64],
+    "ghm_swd_stats": [_p, _p, _i64, _i32, _p, _p],
+    "ghm_swd_project": [_p, _p, _i64, _i32, _p, _i32, _p, _p],
+    "ghm_swd_sort_columns": [_p, _p, _i64, _i32, _i32],
+    "ghm_swd_l1": [_p, _p, _p, _i64, _p, C.POINTER(C.c_double)],
     "ghm_lsgan_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_bce_loss": [_p, _p, _i64, _f, _p, _p, _f, _i32],
     "ghm_recon_loss": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _f, _i32],
@@ -230,7 +236,9 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_split_q_direct": ([_D, _i32], C.c_int),
             "ghm_split_dgrad_dact_supported": ([_D], C.c_int),
             "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64),
-            "ghm_erosion_tile": ([_i32], C.c_int32)}
+            "ghm_erosion_tile": ([_i32], C.c_int32),
+            "ghm_swd_workspace": ([], C.c_int64),
+            "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)
 
 _lib = None

@@ -1169,6 +1169,50 @@ class Ops:
         call("ghm_erosion_emit", self.h, _vp(state_ptr), int(H), int(W), int(pitch), float(height_scale), int(r0), int(c0),
              int(nr), int(nc), int(bool(out_u8)), _vp(out_ptr), int(out_rows), int(out_pitch), int(yoff), int(xoff))
 
+    # sliced Wasserstein distance (csrc/swd.hip, gan_heightmaps_amd/swd.py)
+    @staticmethod
+    def swd_workspace():
+        """bytes of device workspace swd_stats and swd_l1 need"""
+        return int(_lib.load().ghm_swd_workspace())
+
+    @staticmethod
+    def swd_sort_max_chunk():
+        """the longest (padded) column one workgroup sorts in LDS"""
+        return int(_lib.load().ghm_swd_sort_max_chunk())
+
+    def swd_pyramid_level(self, g, pitch, g_next_ptr, next_pitch, lap_ptr, lap_pitch):
+        """g: a DevTensor view [n, C, H, W] of level G_i whose rows lie ``pitch`` cells apart (None: W) -> G_{i+1} at
+        g_next_ptr ([n, C, H/2, next_pitch]; None: the coarsest level, Lap = G) and Lap_i at lap_ptr ([n, C, H, lap_pitch])"""
+        n, Cc, H, W = g.shape
+        pitch = W if pitch is None else int(pitch)
+        call("ghm_swd_pyramid_level", self.h, _vp(g.ptr), n, Cc, H, W, g.nstride, H * pitch, pitch, _vp(g_next_ptr),
+             int(next_pitch), _vp(lap_ptr), int(lap_pitch))
+
+    def swd_gather(self, img_ptr, n, Cc, H, W, pitch, corners_ptr, patches, desc_ptr, row_offset, total_rows):
+        """the C x 7 x 7 windows of the images at img_ptr ([n, C, H, pitch]) at the int32 (row, column) corners on the device
+        -> rows row_offset .. of the [total_rows, 49 C] matrix at desc_ptr"""
+        call("ghm_swd_gather", self.h, _vp(img_ptr), int(n), int(Cc), int(H), int(W), int(pitch), _vp(corners_ptr),
+             int(patches), _vp(desc_ptr), int(row_offset), int(total_rows))
+
+    def swd_stats(self, desc_ptr, N, Cc, stats_ptr, workspace_ptr):
+        """(mean, population standard deviation) per channel of the [N, 49 C] matrix -> 2 C floats at stats_ptr"""
+        call("ghm_swd_stats", self.h, _vp(desc_ptr), int(N), int(Cc), _vp(stats_ptr), _vp(workspace_ptr))
+
+    def swd_project(self, desc_ptr, N, Cc, dirs_ptr, M, stats_ptr, out_ptr):
+        """the normalised [N, 49 C] descriptors times the [49 C, M] directions -> [M, N] at out_ptr"""
+        call("ghm_swd_project", self.h, _vp(desc_ptr), int(N), int(Cc), _vp(dirs_ptr), int(M), _vp(stats_ptr), _vp(out_ptr))
+
+    def swd_sort_columns(self, data_ptr, N, M, chunk=0):
+        """sort each of the M columns of N floats at data_ptr ([M, N]) ascending in place; chunk: the cells a workgroup holds in
+        LDS (0: the largest) -- a longer column goes through the global form"""
+        call("ghm_swd_sort_columns", self.h, _vp(data_ptr), int(N), int(M), int(chunk))
+
+    def swd_l1(self, a_ptr, b_ptr, n, workspace_ptr):
+        """mean |a - b| over n floats, as a Python float (waits for the stream)"""
+        r = C.c_double(0.0)
+        call("ghm_swd_l1", self.h, _vp(a_ptr), _vp(b_ptr), int(n), _vp(workspace_ptr), C.byref(r))
+        return r.value
+
     def lsgan_loss(self, d, target, loss_out, grad=None, grad_scale=1.0, accumulate_loss=False):
         assert d.contiguous
         call("ghm_lsgan_loss", self.h, _vp(d), d.size, target, _vp(loss_out), _vp(grad), grad_scale,

@@ -187,6 +187,97 @@ class Pix2Pix:
                    value_range=(self.is_a_grayscale, self.is_b_grayscale), device=self.device) as scene:
             return scene.render(camera, **kw)
 
+    # ---- sliced Wasserstein distance of the generators (gan_heightmaps_amd/swd.py) ------------------------
+    def _own_draw(self, rs, n):
+        """``self.sampler``'s distribution drawn from the RandomState ``rs``: the samplers of numpy's global RNG (np.random.rand,
+        randn, ...) are methods of a RandomState, and ``rs`` has the same method"""
+        owner, name = getattr(self.sampler, '__self__', None), getattr(self.sampler, '__name__', None)
+        if not isinstance(owner, np.random.RandomState) or not hasattr(rs, name or ''):
+            raise ValueError("swd draws z from a RandomState of its own, which needs a sampler that is a method of numpy's "
+                             "global RNG (np.random.rand, np.random.randn, ...); with %r pass z=[num_images, latent_dim]"
+                             % (self.sampler,))
+        return floatX(getattr(rs, name)(n, self.latent_dim))
+
+    def _swd_real(self, iterator, num_images, batch_size, which, metric):
+        """the real sets' descriptors (set 0) from ``num_images // batch_size`` batches of ``iterator`` -> a dict that
+        _swd_fake compares generated sets with, any number of times; _swd_close frees it.  For 'p2p' the A batches are kept
+        on the host: U(A) is computed from them at every comparison."""
+        from .step import LANE_OF
+        from .swd import SWD, Descriptors
+        if which not in ('both', 'dcgan', 'p2p'):
+            raise ValueError("which must be 'both', 'dcgan' or 'p2p', got %r" % (which,))
+        metric = SWD() if metric is None else metric
+        nb = int(num_images) // int(batch_size)
+        if nb < 1:
+            raise ValueError("num_images=%r gives no batch of %r" % (num_images, batch_size))
+        n, eng, S = nb * batch_size, self.engine, self.in_shp
+        ca, cb = (1 if self.is_a_grayscale else 3), (1 if self.is_b_grayscale else 3)
+        st = {'n': n, 'batch_size': batch_size, 'metric': metric, 'nets': [k for k in ('dcgan', 'p2p') if which in ('both', k)],
+              'A': [], 'real': {}}
+        eng.sync()
+        try:
+            if 'dcgan' in st['nets']:
+                st['real']['dcgan'] = Descriptors(eng.ops[LANE_OF['dcgan_gen']], metric, 0, n, ca, S, S, max_batch=batch_size)
+            if 'p2p' in st['nets']:
+                st['real']['p2p'] = Descriptors(eng.ops[LANE_OF['p2p_gen']], metric, 0, n, cb, S, S, max_batch=batch_size)
+            for _ in range(nb):
+                X, Y = self._next(iterator)
+                X, Y = floatX(X), floatX(Y)
+                if X.shape[0] != batch_size:
+                    raise ValueError("the iterator returned a batch of %d images, not %d (a ragged last batch: choose a "
+                                     "batch size that divides the dataset)" % (X.shape[0], batch_size))
+                if 'dcgan' in st['real']:
+                    st['real']['dcgan'].add(X)
+                if 'p2p' in st['real']:
+                    st['real']['p2p'].add(Y)
+                    st['A'].append(X)
+        except BaseException:
+            self._swd_close(st)
+            raise
+        return st
+
+    def _swd_fake(self, st, seed=0, z=None):
+        """the distance of the current generators' sets (set 1) from the real ones of ``st``"""
+        from .step import LANE_OF
+        from .swd import Descriptors, distance
+        eng, n, bs, S, metric = self.engine, st['n'], st['batch_size'], self.in_shp, st['metric']
+        out = {}
+        for net in st['nets']:
+            key = net + '_gen'
+            real = st['real'][net]
+            if net == 'dcgan':
+                zs = self._own_draw(np.random.RandomState(seed), n) if z is None else floatX(z)
+                if zs.shape != (n, self.latent_dim):
+                    raise ValueError("z must be [%d, %d], got %s" % (n, self.latent_dim, zs.shape))
+            with Descriptors(eng.ops[LANE_OF[key]], metric, 1, n, real.C, S, S, max_batch=bs) as fake:
+                for b in range(n // bs):
+                    inp = zs[b * bs:(b + 1) * bs] if net == 'dcgan' else st['A'][b]
+                    fake.add(eng.generate_device(key, inp, True))          # read from plan.out where it lies
+                out[net] = distance(eng.ops[LANE_OF[key]], real, fake)
+        return out
+
+    @staticmethod
+    def _swd_close(st):
+        for d in st['real'].values():
+            d.close()
+        st['real'], st['A'] = {}, []
+
+    def swd(self, iterator, num_images=1024, batch_size=4, which='both', metric=None, seed=0, z=None):
+        """Sliced Wasserstein distance on Laplacian-pyramid patches between real and generated images, on the GPU
+        (gan_heightmaps_amd/swd.py).  Not in the reference.  'dcgan' compares the iterator's A images with G(z),
+        'p2p' its B images with U(A); ``which`` picks one or 'both'.  Returns {'dcgan': r, 'p2p': r} (or the one asked for),
+        r = {'levels': [512, 256, ...], 'swd': [per level], 'mean': float}; smaller is closer.
+        The iterator is advanced by ``num_images // batch_size`` batches and by nothing else; that many batches of
+        ``batch_size`` images form each set.  z is drawn from a RandomState(seed) of the call's own with ``self.sampler``'s
+        distribution (or given: [num_images, latent_dim]), never from ``self.sampler`` or numpy's global RNG.  metric: a
+        swd.SWD (default SWD()).  The forwards are the deterministic ones (z_fn_det, gen_fn_det) and their outputs are read
+        from device memory; the call works inside ``with model.ema_weights():`` and leaves the training state untouched."""
+        st = self._swd_real(iterator, num_images, batch_size, which, metric)
+        try:
+            return self._swd_fake(st, seed, z)
+        finally:
+            self._swd_close(st)
+
     def ema_weights(self):
         """``with model.ema_weights(): ...`` -- inside the block both generators run on the exponential moving average of
         their parameters (Pix2Pix(ema=decay)): z_fn_det, gen_fn_det, generate_gz / generate_atob / the interpolations with
@@ -329,7 +420,8 @@ class Pix2Pix:
 
     # ---- training loop (pix2pix.py:187-275) ----------------------------------------------------------------
     def train(self, it_train, it_val, batch_size, num_epochs, out_dir, model_dir=None, save_every=10, resume=False,
-              quick_run=False, validate_on_train_iterator=True, dump_images=True, checkpoint_state=False):
+              quick_run=False, validate_on_train_iterator=True, dump_images=True, checkpoint_state=False, swd_every=None,
+              swd_iterator=None, swd_images=1024):
         """Same loop as the reference: per epoch N//batch_size train_fn steps then N//batch_size loss_fn steps,
         a CSV row of epoch means, then the per-epoch image dumps (a 4x4 grid of [A | U(A)] from ``it_val``, one batch of
         A->B pairs from each iterator, 20 DCGAN samples -- pix2pix.py:262-270; they advance the iterators, so they
@@ -339,9 +431,20 @@ class Pix2Pix:
         own loop in tests/test_reference_trainloop.py.
         ``checkpoint_state=True``: the periodic checkpoints are save_checkpoint files (the whole training state, with both
         iterators'); ``resume`` may name either kind -- a state checkpoint continues the run, epoch numbers included, a
-        save_model file loads the parameters only."""
+        save_model file loads the parameters only.
+        ``swd_every=K``: every K epochs ``out_dir/swd.txt`` gets one row per trained generator -- epoch, 'live', net, the sliced
+        Wasserstein distance per level, their mean (Pix2Pix.swd) -- and with ``ema`` a second row, 'ema', of the
+        averaged weights.  The real sets' descriptors are computed once, before the first epoch, from ``swd_images`` images of
+        ``swd_iterator``: an iterator of its own, since drawing from ``it_train`` / ``it_val`` would change the training
+        trajectory (ValueError).  results.txt, the iterators' and the sampler's draws are what they are without it."""
         if getattr(getattr(self, 'engine', None), '_in_ema', False):
             self.engine._live_only("train")
+        if swd_every is not None:
+            if isinstance(swd_every, bool) or not isinstance(swd_every, (int, np.integer)) or swd_every < 1:
+                raise ValueError("swd_every must be None or an integer >= 1, got %r" % (swd_every,))
+            if swd_iterator is None or swd_iterator is it_train or swd_iterator is it_val:
+                raise ValueError("swd_every needs swd_iterator, an iterator of its own: drawing the real sets from it_train "
+                                 "or it_val would change the training trajectory")
 
         def _next(it):
             return next(it) if hasattr(it, '__next__') else it.next()
@@ -417,6 +520,15 @@ class Pix2Pix:
             else:
                 self._set_params(dd, 'both')
             del dd
+        swd_st, swd_f = None, None
+        if swd_every is not None:
+            from . import swd as _swd
+            swd_st = self._swd_real(swd_iterator, swd_images, batch_size, self.train_mode, None)
+            levels = [min(hw) for hw in next(iter(swd_st['real'].values())).sizes]
+            swd_f = open("%s/swd.txt" % out_dir if writer else os.devnull, "w" if not resume else "a")
+            if not resume:
+                swd_f.write(",".join(_swd.header(levels)) + "\n")
+                swd_f.flush()
         for e in range(first, first + num_epochs):
             t0 = time()
             row = [str(e + 1)]
@@ -430,6 +542,15 @@ class Pix2Pix:
             f.write(line + "\n")
             f.flush()
             self._check_loss_scale(e + 1)
+            if swd_st is not None and (e + 1) % swd_every == 0:
+                rows = [('live', self._swd_fake(swd_st))]
+                if getattr(self.engine, 'ema', None) is not None:
+                    with self.ema_weights():
+                        rows.append(('ema', self._swd_fake(swd_st)))
+                for weights, res in rows:
+                    for net in swd_st['nets']:
+                        swd_f.write(",".join(_swd.row(e + 1, weights, net, res[net])) + "\n")
+                swd_f.flush()
             if dump_images:
                 with util_writes(writer):
                     if self.train_mode in ['both', 'p2p']:
@@ -448,6 +569,9 @@ class Pix2Pix:
                 if getattr(getattr(self, 'engine', None), 'ema', None) is not None:
                     self.save_model("%s/%i.ema.model" % (model_dir, e + 1), ema=True)
         f.close()
+        if swd_st is not None:
+            swd_f.close()
+            self._swd_close(swd_st)
 
     def _check_loss_scale(self, epoch):
         """fp16 only: one line per epoch with the dynamic loss scale and the updates it skipped, and a warning when

@@ -794,6 +794,11 @@ class GanStep:
         return self._subgraph[k]
 
     def generate(self, key, inp, deterministic=False):
+        return self.generate_device(key, inp, deterministic).numpy()
+
+    def generate_device(self, key, inp, deterministic=False):
+        """generate() without the download: the forward plan's output DevTensor, enqueued on the net's lane and valid until
+        the next forward of the same (net, batch size, deterministic)"""
         if not deterministic:
             self._live_only("a non-deterministic forward (it moves the BatchNorm running statistics)")
         inp = np.ascontiguousarray(inp, np.float32)
@@ -803,7 +808,7 @@ class GanStep:
         plan.input_nodes[0].out.set(inp)
         for e in prog:
             e[1]()
-        return plan.out.numpy()
+        return plan.out
 
     def generate_chain(self, Z, deterministic=True):
         """z -> G(z) -> U(G(z)) without leaving HBM (the z_fn -> gen_fn chain of generate_interpolation_clip,
