@@ -33,6 +33,8 @@ import sys
 
 import numpy as np
 
+from .util import is_int as _is_int, read_image
+
 __all__ = ["RADIUS", "PLANES", "PARAMS", "DEFAULT_FUSED", "Erosion", "erode", "workspace_planes", "parse_args", "main"]
 
 RADIUS = 3                  # cells one iteration reaches (DESIGN §4p has the derivation)
@@ -43,10 +45,6 @@ PARAMS = ("dt", "rain", "evaporation", "gravity", "pipe", "capacity", "dissolve"
 # the form ``erode`` and the eroded world run by default: the one tools/erosion_bench.py shows faster on the MI355X -- the
 # plain one, 0.130 against 0.144 ms per iteration of a 2304 x 2304 window (DESIGN §4p has the table); both give the same bits
 DEFAULT_FUSED = False
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -201,14 +199,6 @@ def parse_args(argv):
     return a
 
 
-def _read(path):
-    if path.endswith(".npy"):
-        return np.load(path)
-    from PIL import Image
-    Image.MAX_IMAGE_PIXELS = None
-    return np.asarray(Image.open(path).convert("L"))
-
-
 def _write(path, arr, scale_to_max=False):
     if path.endswith(".npy"):
         np.save(path, arr)
@@ -223,7 +213,7 @@ def _write(path, arr, scale_to_max=False):
 def main(argv=None):
     a = parse_args(sys.argv[1:] if argv is None else argv)
     from .device import Device, Ops
-    x = _read(a.input)
+    x = read_image(a.input, "L", mmap=False)
     dev = Device(0)
     try:
         res = erode(Ops(dev), x, a.erosion, fused=True if a.fused else False if a.plain else None,

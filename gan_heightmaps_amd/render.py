@@ -26,6 +26,7 @@ import sys
 import numpy as np
 
 from . import util
+from .util import is_int as _is_int
 
 __all__ = ["DEFAULTS", "MAX_STEPS", "Camera", "Scene", "union_footprint", "parse_args", "main"]
 
@@ -40,10 +41,6 @@ MAX_STEPS = 1 << 20          # samples per ray the kernel accepts (REN_MAX_STEPS
 
 def _num(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
 
 class Camera:
@@ -452,18 +449,8 @@ def frame_names(a):
     return ["%s_%04d.png" % (a.output[:-4], i) for i in range(a.frames)]
 
 
-def _read_image(path):
-    if path.endswith(".npy"):
-        return np.load(path, mmap_mode="r")
-    from PIL import Image
-    Image.MAX_IMAGE_PIXELS = None
-    img = Image.open(path)
-    return np.asarray(img.convert("L" if img.mode in ("L", "1", "I", "I;16", "F") else "RGB"))
-
-
 def main(argv=None):
     a = parse_args(sys.argv[1:] if argv is None else argv)
-    from .terrain import _save_png
     cams = cameras_of(a)
     kw = dict(shadows=not a.no_shadows, haze=a.haze, step=a.step, max_dist=a.max_dist)
     if a.sun is not None:
@@ -484,14 +471,14 @@ def main(argv=None):
                 fkw = {k: v for k, v in kw.items() if k != "max_dist"}
                 for name, img in zip(frame_names(a), world.flight(cams, a.max_dist, window_mb=a.window_mb,
                                                                   height_scale=a.height_scale, **fkw)):
-                    _save_png(name, img)
+                    util.save_png(name, img)
                 return 0
             # one scene over the union of the frames' footprints
             scene = world.scene(*union_footprint([c.footprint(a.max_dist) for c in cams]), height_scale=a.height_scale)
         else:
-            scene = Scene(_read_image(a.heightmap), _read_image(a.texture), height_scale=a.height_scale)
+            scene = Scene(util.read_image(a.heightmap), util.read_image(a.texture), height_scale=a.height_scale)
         for cam, name in zip(cams, frame_names(a)):
-            _save_png(name, scene.render(cam, **kw))
+            util.save_png(name, scene.render(cam, **kw))
     finally:
         if scene is not None:
             scene.close()

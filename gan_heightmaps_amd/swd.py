@@ -30,16 +30,14 @@ import sys
 
 import numpy as np
 
+from .util import is_int as _is_int
+
 __all__ = ["PATCH", "MAX_CHANNELS", "SWD", "Descriptors", "distance", "compare", "corners", "directions", "header", "row",
            "parse_args", "main"]
 
 PATCH = 7                   # GHM_SWD_PATCH
 MAX_CHANNELS = 4            # GHM_SWD_MAX_K / 49
 MIN_SIZE = 16               # the short side of the coarsest level is at least this
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
 
 @dataclasses.dataclass(frozen=True)

@@ -30,7 +30,11 @@ import sys
 import numpy as np
 
 from . import layers as L
+from . import util
 from .architectures.layers import BilinearUpsample2DLayer
+from .streaming import DownloadRing, check_uint8_channels, output_array, store_rows
+
+_save_png = util.save_png          # (tools/render_bench.py imports the writer under this name)
 
 __all__ = ["BLENDS", "WINDOW_BUDGET", "split_generator", "trunk_halo", "trunk_scale", "window_plan", "axis_blend",
            "TerrainGeometry", "generate_terrain", "parse_cells", "parse_args", "main"]
@@ -193,7 +197,6 @@ def generate_terrain(engine, gen_out, latent_dim, sampler, is_a_grayscale, grid=
                      out=None, uint8=False, deterministic=True):
     """A (out gy) x (out gx) heightmap from a grid of latent vectors with the DCGAN generator of ``engine`` (a GanStep).
     See Pix2Pix.generate_terrain."""
-    from .device import PinnedArray
     from .step import LANE_OF
     if not deterministic:
         raise NotImplementedError("generate_terrain needs deterministic=True: with batch statistics a window's output would "
@@ -203,16 +206,11 @@ def generate_terrain(engine, gen_out, latent_dim, sampler, is_a_grayscale, grid=
     gy, gx, z = _check_grid(grid, z, latent_dim)
     geo = TerrainGeometry(gen_out, gy, gx, band)
     C, H, W = geo.channels, geo.H, geo.W
-    if uint8 and C not in (1, 3):
-        raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % C)
     if uint8:
-        shape, dtype = ((H, W) if C == 1 else (H, W, 3)), np.uint8
+        check_uint8_channels(C)
+        out = output_array(out, (H, W) if C == 1 else (H, W, 3), np.uint8)
     else:
-        shape, dtype = (C, H, W), np.float32
-    if out is None:
-        out = np.empty(shape, dtype)
-    elif tuple(out.shape) != shape or out.dtype != dtype:
-        raise ValueError("out must be %s %s, got %s %s" % (np.dtype(dtype), shape, out.dtype, tuple(out.shape)))
+        out = output_array(out, (C, H, W), np.float32)
     if z is None:
         z = np.asarray(sampler(gy * gx, latent_dim), np.float32).reshape(gy, gx, latent_dim)
     zf = np.ascontiguousarray(z.reshape(gy * gx, latent_dim), np.float32)
@@ -231,9 +229,8 @@ def generate_terrain(engine, gen_out, latent_dim, sampler, is_a_grayscale, grid=
     stage_rows = geo.win * F
     engine.sync()
     P = dev.empty((n, geo.nch * geo.s * geo.s, 1, 1))
-    ostage, pin = [], []
     cp = type(dev)(dev.index)                # the copy stream: finished rows go down while the next window runs
-    ev_fin, ev_down = [dev.event_create() for _ in range(2)], [cp.event_create() for _ in range(2)]
+    down = None
     try:
         # the head, once for every cell: P stays resident
         for c0 in range(0, n, Bh):
@@ -244,50 +241,22 @@ def generate_terrain(engine, gen_out, latent_dim, sampler, is_a_grayscale, grid=
             for e in hprog:
                 e[1]()
             ops.copy_view(hout.samples(0, m), P.samples(c0, c0 + m))
-        ostage = [dev.alloc(stage_rows * W * bpp) for _ in range(2)]
-        pin = [PinnedArray((stage_rows * W * bpp,), np.uint8) for _ in range(2)]
-
-        def drain(item):
-            slot, ya, yb = item
-            dev.event_sync(ev_down[slot])
-            k = yb - ya
-            a = pin[slot].array[:k * W * bpp]
-            if not uint8:
-                out[:, ya:yb, :] = a.view(np.float32).reshape(C, k, W)
-            elif C == 1:
-                out[ya:yb] = a.reshape(k, W)
-            else:
-                out[ya:yb] = a.reshape(k, W, 3)
-
-        pending = []
-        for i, (w0, klo, khi) in enumerate(geo.windows):
-            slot = i % 2
+        down = DownloadRing(dev, cp, stage_rows * W * bpp, lambda buf, ya, yb: store_rows(out, buf, ya, yb, W))
+        for w0, klo, khi in geo.windows:
             ops.terrain_seed(P, gy, gx, geo.s, w0, geo.win, blend == 'bilinear', inp)
             for e in tprog:
                 e[1]()
-            if i >= 2:
-                dev.event_wait(ev_down[slot])                # the stage's previous download has left
             r0, nr = (klo - w0) * F, (khi - klo) * F
-            ops.terrain_emit(u, r0, nr, uint8, is_a_grayscale, ostage[slot])
-            dev.event_record(ev_fin[slot])
-            cp.event_wait(ev_fin[slot])
-            cp.d2h_async(pin[slot], ostage[slot], nr * W * bpp)
-            cp.event_record(ev_down[slot])
-            pending.append((slot, klo * F, khi * F))
-            while len(pending) > 1:
-                drain(pending.pop(0))
-        while pending:
-            drain(pending.pop(0))
+            ops.terrain_emit(u, r0, nr, uint8, is_a_grayscale, down.stage())
+            down.send(nr * W * bpp, klo * F, khi * F)
+            down.poll()
+        down.finish()
         engine.sync()
     finally:
         dev.sync()
         cp.sync()
-        for e in ev_fin + ev_down:
-            dev.event_destroy(e)
-        for p in pin:
-            p.close()
-        for p in ostage:
-            dev.free(p)
+        if down is not None:
+            down.close()
         dev.free(P.ptr)
         cp.close()
     return out
@@ -329,14 +298,8 @@ def parse_args(argv):
     return a
 
 
-def _save_png(path, arr):
-    from PIL import Image
-    Image.fromarray(np.ascontiguousarray(arr)).save(path)
-
-
 def main(argv=None):
     a = parse_args(sys.argv[1:] if argv is None else argv)
-    from . import util
     from .experiments import make_model
     model = make_model(a.experiment, dtype=a.dtype, verbose=False)
     model.load_model(a.model, mode='both' if a.texture else 'dcgan')
@@ -352,7 +315,7 @@ def main(argv=None):
         hm.flush()
     else:
         img = util.to_uint8(util.convert_to_rgb(hm, is_grayscale=model.is_a_grayscale))
-        _save_png(a.output, img[:, :, 0] if geo.channels == 1 else img)
+        util.save_png(a.output, img[:, :, 0] if geo.channels == 1 else img)
     if a.texture:
         tex = np.lib.format.open_memmap(a.texture, mode="w+", dtype=np.uint8, shape=(geo.H, geo.W, 3)) \
             if a.texture.endswith(".npy") else None
@@ -360,7 +323,7 @@ def main(argv=None):
         if a.texture.endswith(".npy"):
             tex.flush()
         else:
-            _save_png(a.texture, tex)
+            util.save_png(a.texture, tex)
     model.device.close()
     return 0
 

@@ -25,6 +25,9 @@ import sys
 
 import numpy as np
 
+from .streaming import DownloadRing, check_uint8_channels, output_array, shift_accumulator, store_rows
+from .util import read_image, save_png
+
 __all__ = ["AxisPlan", "axis_plan", "axis_weights", "reflect_index", "tile_batches", "check_overlap", "texture_heightmap",
            "parse_args", "main"]
 
@@ -127,36 +130,34 @@ def _input_layout(heightmap, channels):
 
 
 class _Tiler:
-    """the device and page-locked buffers of one texture_heightmap call (all O(T W), none depends on H)"""
+    """the device and page-locked buffers of one texture_heightmap call (all O(T W), none depends on H): the input bands, the
+    accumulator, and the download ring (``down``) that stores finished rows into ``out``"""
 
-    def __init__(self, dev, W, T, c_in, c_out, u8_in, u8_out):
+    def __init__(self, dev, W, T, c_in, c_out, u8_in, u8_out, out):
         from .device import PinnedArray
+        mkpin = getattr(type(dev), 'pinned_array', PinnedArray)
         self.dev = dev
         self.cp = type(dev)(dev.index)         # the copy stream: uploads and downloads overlap the tile rows
         self.band_bytes = c_in * T * W * (1 if u8_in else 4)
         self.acc_bytes = c_out * T * W * 4
-        self.out_bytes = T * W * (3 if u8_out else 4 * c_out)
         self.band = [dev.alloc(self.band_bytes) for _ in range(2)]
         self.acc = dev.alloc(self.acc_bytes)
-        self.ostage = [dev.alloc(self.out_bytes) for _ in range(2)]
-        self.device_bytes = 2 * self.band_bytes + self.acc_bytes + 2 * self.out_bytes
-        self.pin_in = [PinnedArray((self.band_bytes,), np.uint8) for _ in range(2)]
-        self.pin_out = [PinnedArray((self.out_bytes,), np.uint8) for _ in range(2)]
-        ev = dev.event_create
+        self.down = DownloadRing(dev, self.cp, T * W * (3 if u8_out else 4 * c_out),
+                                 lambda buf, ya, yb: store_rows(out, buf, ya, yb, W))
+        self.pin_in = [mkpin((self.band_bytes,), np.uint8) for _ in range(2)]
         self.ev_land = [self.cp.event_create() for _ in range(2)]     # band upload landed (copy stream)
-        self.ev_used = [ev() for _ in range(2)]                       # last gather of a band (compute stream)
-        self.ev_fin = [ev() for _ in range(2)]                        # rows finalized into an output stage
-        self.ev_down = [self.cp.event_create() for _ in range(2)]     # output stage downloaded
+        self.ev_used = [dev.event_create() for _ in range(2)]         # last gather of a band (compute stream)
 
     def close(self):
         self.dev.sync()
         self.cp.sync()
-        for e in self.ev_land + self.ev_used + self.ev_fin + self.ev_down:
+        for e in self.ev_land + self.ev_used:
             self.dev.event_destroy(e)
-        for p in self.pin_in + self.pin_out:
+        for p in self.pin_in:
             p.close()
-        for p in self.band + [self.acc] + self.ostage:
+        for p in self.band + [self.acc]:
             self.dev.free(p)
+        self.down.close()
         self.cp.close()
 
 
@@ -179,17 +180,13 @@ def texture_heightmap(engine, heightmap, is_a_grayscale, is_b_grayscale, overlap
     heightmap = heightmap if hasattr(heightmap, 'dtype') else np.asarray(heightmap)
     H, W, u8_in = _input_layout(heightmap, c_in)
     py, px = axis_plan(H, T, o), axis_plan(W, T, o)
-    if uint8 and c_out not in (1, 3):
-        raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % c_out)
-    shape, dtype = ((H, W, 3), np.uint8) if uint8 else ((c_out, H, W), np.float32)
-    if out is None:
-        out = np.empty(shape, dtype)
-    elif tuple(out.shape) != shape or out.dtype != dtype:
-        raise ValueError("out must be %s %s, got %s %s" % (np.dtype(dtype), shape, out.dtype, tuple(out.shape)))
+    if uint8:
+        check_uint8_channels(c_out)
+    out = output_array(out, *(((H, W, 3), np.uint8) if uint8 else ((c_out, H, W), np.float32)))
     s, ny, nx = T - o, py.n, px.n
     batches = tile_batches(nx, int(batch_size))
     engine.sync()
-    tl = _Tiler(dev, W, T, c_in, c_out, u8_in, uint8)
+    tl = _Tiler(dev, W, T, c_in, c_out, u8_in, uint8, out)
     try:
         dev.memset_zero(tl.acc, tl.acc_bytes)
         def upload(iy, slot):
@@ -206,17 +203,8 @@ def texture_heightmap(engine, heightmap, is_a_grayscale, is_b_grayscale, overlap
             tl.cp.event_record(tl.ev_land[slot])
             return lo, hi - lo
 
-        def drain(item):
-            oslot, ya, yb = item
-            dev.event_sync(tl.ev_down[oslot])
-            n = yb - ya
-            if uint8:
-                out[ya:yb] = tl.pin_out[oslot].array[:n * W * 3].reshape(n, W, 3)
-            else:
-                out[:, ya:yb, :] = tl.pin_out[oslot].array[:c_out * n * W * 4].view(np.float32).reshape(c_out, n, W)
-
         bands = [upload(0, 0), None]
-        pending, finals, used = [], 0, [False, False]
+        used = [False, False]
         for iy in range(ny):
             slot, y0 = iy % 2, py.start(iy)
             band_row0, band_rows = bands[slot]
@@ -233,35 +221,18 @@ def texture_heightmap(engine, heightmap, is_a_grayscale, is_b_grayscale, overlap
             last = iy == ny - 1
             r_lo, r_hi = max(0, -y0), min(T if last else s, H - y0)
             if r_hi > r_lo:
-                oslot = finals % 2
-                if finals >= 2:
-                    dev.event_wait(tl.ev_down[oslot])          # the stage's previous download has left
                 ops.texture_finalize(tl.acc, W, T, c_out, r_lo, r_hi - r_lo, y0, ny, py.pad, nx, px.pad, o, uint8,
-                                     is_b_grayscale, tl.ostage[oslot])
-                dev.event_record(tl.ev_fin[oslot])
-                tl.cp.event_wait(tl.ev_fin[oslot])
-                nbytes = (r_hi - r_lo) * W * (3 if uint8 else 4 * c_out)
-                tl.cp.d2h_async(tl.pin_out[oslot], tl.ostage[oslot], nbytes)
-                tl.cp.event_record(tl.ev_down[oslot])
-                pending.append((oslot, y0 + r_lo, y0 + r_hi))
-                finals += 1
+                                     is_b_grayscale, tl.down.stage())
+                tl.down.send((r_hi - r_lo) * W * (3 if uint8 else 4 * c_out), y0 + r_lo, y0 + r_hi)
             if not last:
-                # the o rows shared with the next tile row move to the top of the accumulator, the rest restarts at 0
-                row = W * 4
-                for c in range(c_out):
-                    base = tl.acc + c * T * row
-                    if o:
-                        dev.d2d(base, base + s * row, o * row)
-                    dev.memset_zero(base + o * row, (T - o) * row)
+                shift_accumulator(dev, tl.acc, c_out, T, W * 4, o)
                 nslot = (iy + 1) % 2
                 if used[nslot]:
                     tl.cp.event_wait(tl.ev_used[nslot])        # the band's previous tile row has gathered from it
                     dev.event_sync(tl.ev_land[nslot])          # and its page-locked source may be refilled
                 bands[nslot] = upload(iy + 1, nslot)
-            while len(pending) > 1:
-                drain(pending.pop(0))
-        while pending:
-            drain(pending.pop(0))
+            tl.down.poll()             # here, behind the shift and the next upload: the host blocks with work enqueued
+        tl.down.finish()
         engine.sync()
     finally:
         tl.close()
@@ -289,14 +260,8 @@ def parse_args(argv):
 
 
 def read_heightmap(path, channels):
-    """PNG through PIL (no decompression-bomb limit: a whole-planet map is hundreds of megapixels) or .npy through mmap"""
-    if path.endswith(".npy"):
-        return np.load(path, mmap_mode="r")
-    from PIL import Image
-    Image.MAX_IMAGE_PIXELS = None
-    img = Image.open(path)
-    img = img.convert("L" if channels == 1 else "RGB")
-    return np.asarray(img)
+    """PNG through PIL as grey or RGB, or .npy through mmap"""
+    return read_image(path, "L" if channels == 1 else "RGB")
 
 
 def main(argv=None):
@@ -316,8 +281,7 @@ def main(argv=None):
     if out is not None:
         out.flush()
     else:
-        from PIL import Image
-        Image.fromarray(tex).save(a.output)
+        save_png(a.output, tex)
     model.device.close()
     return 0
 

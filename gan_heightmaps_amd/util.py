@@ -85,6 +85,29 @@ def imread(fname):
     return np.asarray(Image.open(fname))
 
 
+def is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def read_image(path, mode=None, mmap=True):
+    """a .npy as it is (through mmap unless mmap=False), or an image through PIL with no decompression-bomb limit (a
+    whole-planet map is hundreds of megapixels), converted to ``mode`` ('L' / 'RGB'; default: 'L' for a one-band file, 'RGB'
+    for any other)"""
+    if path.endswith(".npy"):
+        return np.load(path, mmap_mode="r" if mmap else None)
+    from PIL import Image
+    Image.MAX_IMAGE_PIXELS = None
+    img = Image.open(path)
+    if mode is None:
+        mode = "L" if img.mode in ("L", "1", "I", "I;16", "F") else "RGB"
+    return np.asarray(img.convert(mode))
+
+
+def save_png(path, arr):
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(arr)).save(path)
+
+
 def plot_grid(out_filename, itr, out_fn, is_a_grayscale, is_b_grayscale, N=4):
     """N x N figure of [A | B] pairs (util.py:101-116): one batch is drawn per cell, ``out_fn`` maps A -> B
     (``None`` shows the iterator's own B), only element 0 of each batch is shown."""

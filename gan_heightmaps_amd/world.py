@@ -43,9 +43,11 @@ import numpy as np
 
 from . import erosion as _erosion
 from . import layers as L
+from .streaming import DownloadRing, check_uint8_channels, output_array, shift_accumulator, store_rows
 from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
 from . import terrain as _terrain
 from .texture import check_overlap
+from .util import is_int as _is_int
 
 __all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
            "window_elements", "default_chunk_cells", "slot_batches", "erosion_sources", "snap_out", "plan_windows", "TerrainWorld",
@@ -54,10 +56,6 @@ __all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "world_latent", "
 
 HEAD_BLOCK = 8                   # the head runs over world-aligned blocks of HEAD_BLOCK x HEAD_BLOCK cells, one pass each
 MAX_BATCH = 32                   # GHM_WORLD_MAX_TILES (include/ghm.h): tiles per forward pass
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
 
 def world_latent(seed, i, j, sampler, latent_dim):
@@ -174,120 +172,64 @@ def plan_windows(footprints, snap, max_pixels):
 
 
 class _HostSinks:
-    """Where a request's finished rows go, the host form: a device stage -> a pinned buffer -> the caller's arrays, two of each
-    per output, the downloads on a copy stream of their own so that finished rows go down while the next chunks run."""
+    """Where a request's finished rows go, the host form: one download ring per output (streaming.DownloadRing) into the
+    caller's arrays, both on one copy stream of their own so that finished rows go down while the next chunks run."""
 
-    def __init__(self, world, rect, alloc, out_hm, out_tex, hm_u8, tex_u8):
-        self.world, self.rect, self.alloc = world, rect, alloc
+    def __init__(self, world, rect, out_hm, out_tex, hm_u8, tex_u8):
+        self.world, self.rect = world, rect
         self.out_hm, self.out_tex, self.hm_u8, self.tex_u8 = out_hm, out_tex, hm_u8, tex_u8
         self.cp = type(world._dev)(world._dev.index)
-        self.pins, self.events = [], []
-        self.hdone, self.hpending, self.tpending, self.finals = [], [], [], 0
-
-    def _pinned(self, n):
-        from .device import PinnedArray
-        self.pins.append(PinnedArray((n,), np.uint8))
-        return self.pins[-1]
-
-    def _event(self, d):
-        self.events.append(d.event_create())
-        return self.events[-1]
+        self.hm = self.tex = None
+        self.hdone = []
 
     def begin_hm(self):
-        wd, (y0, x0, h, w) = self.world, self.rect
-        C, dev = wd._geo.channels, wd._dev
+        wd, (y0, x0, h, w), out = self.world, self.rect, self.out_hm
+        C = wd._geo.channels
         self.hbpp = (1 if C == 1 else 3) if self.hm_u8 else 4 * C
-        hrows = min(wd._K, h)
-        self.hstage = [self.alloc(dev, hrows * w * self.hbpp) for _ in range(2)]
-        self.hpin = [self._pinned(hrows * w * self.hbpp) for _ in range(2)]
-        self.hfin, self.hdown = [self._event(dev) for _ in range(2)], [self._event(self.cp) for _ in range(2)]
+        self.hm = DownloadRing(wd._dev, self.cp, min(wd._K, h) * w * self.hbpp,
+                               lambda buf, ya, yb: store_rows(out, buf, ya, yb, w))
 
     def begin_tex(self, c_out, Wp):
-        wd = self.world
-        T, udev = wd._geo.out, wd._udev
+        wd, w, out = self.world, self.rect[3], self.out_tex
         self.c_out, self.Wp = c_out, Wp
         self.tbpp = 3 if self.tex_u8 else 4 * c_out
-        self.tstage = [self.alloc(udev, T * Wp * self.tbpp) for _ in range(2)]
-        self.tpin = [self._pinned(T * Wp * self.tbpp) for _ in range(2)]
-        self.tfin, self.tdown = [self._event(udev) for _ in range(2)], [self._event(self.cp) for _ in range(2)]
-
-    def _hm_drain(self, item):
-        slot, ya, yb = item
-        C, w, out_hm = self.world._geo.channels, self.rect[3], self.out_hm
-        self.world._dev.event_sync(self.hdown[slot])
-        k = yb - ya
-        a = self.hpin[slot].array[:k * w * self.hbpp]
-        if not self.hm_u8:
-            out_hm[:, ya:yb, :] = a.view(np.float32).reshape(C, k, w)
-        elif C == 1:
-            out_hm[ya:yb] = a.reshape(k, w)
-        else:
-            out_hm[ya:yb] = a.reshape(k, w, 3)
+        self.tex = DownloadRing(wd._udev, self.cp, wd._geo.out * Wp * self.tbpp,
+                                lambda buf, ya, yb: store_rows(out, buf, ya, yb, Wp, w))
 
     def hm_row(self, a, b_lo, b_hi):
         """the request's rows inside chunk row a (its chunks are resident) -> a stage -> the host"""
-        wd, (y0, x0, h, w), cp = self.world, self.rect, self.cp
-        dev, ops, K, C = wd._dev, wd._ops, wd._K, wd._geo.channels
-        slot = len(self.hdone) % 2
+        wd, (y0, x0, h, w) = self.world, self.rect
+        K, C = wd._K, wd._geo.channels
         ra, rb = max(y0, a * K), min(y0 + h, (a + 1) * K)
-        if len(self.hdone) >= 2:
-            dev.event_wait(self.hdown[slot])                 # the stage's previous download has left
+        stage = self.hm.stage()
         for b in range(b_lo, b_hi + 1):
             ca, cb = max(x0, b * K), min(x0 + w, (b + 1) * K)
-            ops.world_crop(wd._chunks[(a, b)], C, K, ra - a * K, ca - b * K, rb - ra, cb - ca, self.hm_u8,
-                           wd.model.is_a_grayscale, self.hstage[slot], w, ca - x0)
-        dev.event_record(self.hfin[slot])
-        cp.event_wait(self.hfin[slot])
-        cp.d2h_async(self.hpin[slot], self.hstage[slot], (rb - ra) * w * self.hbpp)
-        cp.event_record(self.hdown[slot])
+            wd._ops.world_crop(wd._chunks[(a, b)], C, K, ra - a * K, ca - b * K, rb - ra, cb - ca, self.hm_u8,
+                               wd.model.is_a_grayscale, stage, w, ca - x0)
+        self.hm.send((rb - ra) * w * self.hbpp, ra - y0, rb - y0)
         self.hdone.append(a)
-        self.hpending.append((slot, ra - y0, rb - y0))
-        while len(self.hpending) > 1:
-            self._hm_drain(self.hpending.pop(0))
-
-    def _tex_drain(self, item):
-        slot, ya, yb = item
-        c_out, Wp, w, out_tex = self.c_out, self.Wp, self.rect[3], self.out_tex
-        self.world._udev.event_sync(self.tdown[slot])
-        n = yb - ya
-        if self.tex_u8:
-            out_tex[ya:yb] = self.tpin[slot].array[:n * Wp * 3].reshape(n, Wp, 3)[:, :w]
-        else:
-            out_tex[:, ya:yb, :] = self.tpin[slot].array[:c_out * n * Wp * 4].view(np.float32) \
-                .reshape(c_out, n, Wp)[:, :, :w]
+        self.hm.poll()
 
     def tex_rows(self, acc, r_lo, n, yr, ny, pad_y, nx, pad_x):
         """rows [r_lo, r_lo + n) of the accumulator, the request's rows yr + r_lo ..., finalized -> a stage -> the host"""
-        wd, cp = self.world, self.cp
-        udev = wd._udev
-        slot = self.finals % 2
-        if self.finals >= 2:
-            udev.event_wait(self.tdown[slot])
+        wd = self.world
         wd._uops.texture_finalize(acc, self.Wp, wd._geo.out, self.c_out, r_lo, n, yr, ny, pad_y, nx, pad_x, wd.overlap,
-                                  self.tex_u8, wd.model.is_b_grayscale, self.tstage[slot])
-        udev.event_record(self.tfin[slot])
-        cp.event_wait(self.tfin[slot])
-        cp.d2h_async(self.tpin[slot], self.tstage[slot], n * self.Wp * self.tbpp)
-        cp.event_record(self.tdown[slot])
-        self.tpending.append((slot, yr + r_lo, yr + r_lo + n))
-        self.finals += 1
+                                  self.tex_u8, wd.model.is_b_grayscale, self.tex.stage())
+        self.tex.send(n * self.Wp * self.tbpp, yr + r_lo, yr + r_lo + n)
 
     def tex_poll(self):
-        while len(self.tpending) > 1:
-            self._tex_drain(self.tpending.pop(0))
+        self.tex.poll()
 
     def finish(self):
-        while self.tpending:
-            self._tex_drain(self.tpending.pop(0))
-        while self.hpending:
-            self._hm_drain(self.hpending.pop(0))
+        for ring in (self.tex, self.hm):
+            if ring is not None:
+                ring.finish()
 
     def close(self):
         self.cp.sync()
-        for e in self.events:
-            self.world._dev.event_destroy(e)
-        for p in self.pins:
-            p.close()
+        for ring in (self.hm, self.tex):
+            if ring is not None:
+                ring.close()
         self.cp.close()
 
 
@@ -650,14 +592,6 @@ class TerrainWorld:
             raise ValueError("the region (%d, %d, %d, %d) lies outside the kernels' int32 seed coordinates" % (y0, x0, h, w))
         return int(y0), int(x0), int(h), int(w)
 
-    @staticmethod
-    def _out(out, shape, dtype):
-        if out is None:
-            return np.empty(shape, dtype)
-        if tuple(out.shape) != shape or out.dtype != dtype:
-            raise ValueError("out must be %s %s, got %s %s" % (np.dtype(dtype), shape, out.dtype, tuple(out.shape)))
-        return out
-
     def heightmap(self, y0, x0, h, w, out=None, uint8=False):
         """pixels [y0, y0 + h) x [x0, x0 + w) of the heightmap: (C_a, h, w) float32, or with uint8=True
         util.to_uint8(util.convert_to_rgb(.)) as (h, w) for a greyscale generator, (h, w, 3) otherwise"""
@@ -759,10 +693,10 @@ class TerrainWorld:
         geo, K = self._geo, self._K
         C = geo.channels
         if want_hm and scene is None:
-            if hm_u8 and C not in (1, 3):
-                raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % C)
+            if hm_u8:
+                check_uint8_channels(C)
             shape = ((h, w) if C == 1 else (h, w, 3)) if hm_u8 else (C, h, w)
-            out_hm = self._out(out_hm, shape, np.uint8 if hm_u8 else np.float32)
+            out_hm = output_array(out_hm, shape, np.uint8 if hm_u8 else np.float32)
         self._bind()
         eng, udev, uops = self._eng, self._udev, self._uops
         T, o, B = geo.out, self.overlap, self.batch_size
@@ -775,20 +709,15 @@ class TerrainWorld:
                 raise ValueError("the pix2pix generator takes %d x %d x %d tiles, the heightmap generator makes %d x %d x %d"
                                  % (inp.Cc, inp.H, inp.W, C, T, T))
             if scene is None:
-                if tex_u8 and c_out not in (1, 3):
-                    raise ValueError("uint8 output needs a 1- or 3-channel generator, this one has %d" % c_out)
-                out_tex = self._out(out_tex, (h, w, 3) if tex_u8 else (c_out, h, w), np.uint8 if tex_u8 else np.float32)
+                if tex_u8:
+                    check_uint8_channels(c_out)
+                out_tex = output_array(out_tex, (h, w, 3) if tex_u8 else (c_out, h, w), np.uint8 if tex_u8 else np.float32)
         a_lo, a_hi = axis_chunks(y0, h, K)
         b_lo, b_hi = axis_chunks(x0, w, K)
         eng.sync()
-        devbufs = []
-
-        def alloc(d, n):
-            devbufs.append((d, d.alloc(n)))
-            return devbufs[-1][1]
-
+        acc = None
         if scene is None:
-            sink = _HostSinks(self, (y0, x0, h, w), alloc, out_hm, out_tex, hm_u8, tex_u8)
+            sink = _HostSinks(self, (y0, x0, h, w), out_hm, out_tex, hm_u8, tex_u8)
         else:
             sink = _SceneSinks(self, (y0, x0, h, w), *scene)
         try:
@@ -809,7 +738,7 @@ class TerrainWorld:
                 tb_lo, tb_hi = (q_lo * st) // K, (q_hi * st + T - 1) // K
                 batches = slot_batches(q_lo, q_hi, B)
                 acc_bytes = c_out * T * Wp * 4
-                acc = alloc(udev, acc_bytes)
+                acc = udev.alloc(acc_bytes)
                 sink.begin_tex(c_out, Wp)
                 udev.memset_zero(acc, acc_bytes)
 
@@ -844,20 +773,15 @@ class TerrainWorld:
                     if r_hi > r_lo:
                         sink.tex_rows(acc, r_lo, r_hi - r_lo, yr, ny, pad_y, nx, pad_x)
                     if not last:
-                        row = Wp * 4
-                        for c in range(c_out):
-                            base = acc + c * T * row
-                            if o:
-                                udev.d2d(base, base + st * row, o * row)
-                            udev.memset_zero(base + o * row, (T - o) * row)
+                        shift_accumulator(udev, acc, c_out, T, Wp * 4, o)
                     sink.tex_poll()
             sink.finish()
             eng.sync()
         finally:
             eng.sync()
             sink.close()
-            for d, p in devbufs:
-                d.free(p)
+            if acc is not None:
+                udev.free(acc)
             self._release()
         return out_hm, out_tex
 
@@ -916,7 +840,6 @@ def main(argv=None):
     a = parse_args(sys.argv[1:] if argv is None else argv)
     from . import util
     from .experiments import make_model
-    from .terrain import _save_png
     model = make_model(a.experiment, dtype=a.dtype, verbose=False)
     model.load_model(a.model, mode='both' if a.texture else 'dcgan')
     y0, x0, h, w = a.region
@@ -937,12 +860,12 @@ def main(argv=None):
         hm.flush()
     else:
         img = util.to_uint8(util.convert_to_rgb(hm, is_grayscale=model.is_a_grayscale))
-        _save_png(a.output, img[:, :, 0] if C == 1 else img)
+        util.save_png(a.output, img[:, :, 0] if C == 1 else img)
     if a.texture:
         if a.texture.endswith(".npy"):
             tex.flush()
         else:
-            _save_png(a.texture, tex)
+            util.save_png(a.texture, tex)
     model.device.close()
     return 0
 

@@ -373,3 +373,174 @@ def host_device_class():
             pass
 
     return HostDevice
+
+
+# ---- a tracing device: every call a streaming pipeline makes on its contexts and ops, in host order, as JSON-ready rows
+# ---- [method, context, integer arguments ...].  Contexts made by ``type(dev)(index)`` log into the same list, so the order
+# ---- across streams is visible.  Pointers are written as "p<k>+<offset>" (k-th allocation), events and page-locked
+# ---- buffers as "ev<k>" / "pin<k>" by first appearance in the log.  What no stream can observe -- making and destroying
+# ---- events, making and closing page-locked buffers, frees (all behind a sync) -- is counted in ``tally``, not ordered.
+def trace_device_class():
+    import bisect
+    from collections import Counter
+
+    class Shared:
+        log, tally, bases, sizes, names, nctx = [], Counter(), [], [], {}, 0
+
+    ARENA = 1 << 40
+
+    def ptr(p):
+        i = bisect.bisect_right(Shared.bases, p) - 1
+        assert i >= 0 and p - Shared.bases[i] <= Shared.sizes[i], "a pointer outside every allocation"
+        return "p%d+%d" % (i, p - Shared.bases[i])
+
+    def name(kind, obj):
+        # (the object is kept, so that its id is not handed out again)
+        return Shared.names.setdefault((kind, id(obj)), ("%s%d" % (kind, sum(k[0] == kind for k in Shared.names)), obj))[0]
+
+    def norm(v):
+        if isinstance(v, DevTensor):
+            return ["T", ptr(v.ptr), list(v.shape), v.nstride]
+        if isinstance(v, (bool, np.bool_)):
+            return bool(v)
+        if isinstance(v, (int, np.integer)):
+            return ptr(int(v)) if v >= ARENA else int(v)
+        if isinstance(v, (list, tuple)):
+            return [norm(x) for x in v]
+        return v if v is None or isinstance(v, str) else repr(v)
+
+    class Event:
+        pass
+
+    class TraceOps:
+        def __init__(self, dev):
+            self.dev = dev
+
+        def __getattr__(self, method):
+            def rec(*args, **kw):
+                assert not kw
+                Shared.log.append([method, self.dev.name] + [norm(a) for a in args])
+            return rec
+
+    class TraceDevice:
+        ops_class = TraceOps
+        shared = Shared
+
+        def __init__(self, index=0):
+            self.h, self.index = None, index
+            self.name = "ctx%d" % Shared.nctx
+            Shared.nctx += 1
+            Shared.log.append(["ctx_create", self.name, index])
+
+        def _log(self, method, *args):
+            Shared.log.append([method, self.name] + list(args))
+
+        def alloc(self, nbytes):
+            base = (Shared.bases[-1] + Shared.sizes[-1] + 4096) // 256 * 256 if Shared.bases else ARENA
+            Shared.bases.append(base)
+            Shared.sizes.append(int(nbytes))
+            self._log("alloc", int(nbytes))
+            return base
+
+        def free(self, p):
+            Shared.tally["free", self.name, Shared.sizes[Shared.bases.index(p)]] += 1
+
+        def empty(self, shape):
+            shape = tuple(int(s) for s in shape)
+            n = int(np.prod(shape))
+            return DevTensor(self, self.alloc(4 * n), shape if len(shape) in (2, 4) else (1, n, 1, 1))
+
+        def h2d(self, p, arr):
+            self._log("h2d", ptr(p), int(np.asarray(arr).nbytes))
+
+        def memset_zero(self, p, nbytes):
+            self._log("memset_zero", ptr(p), int(nbytes))
+
+        def d2d(self, dst, src, nbytes):
+            self._log("d2d", ptr(dst), ptr(src), int(nbytes))
+
+        def h2d_async(self, p, pinned, nbytes=None):
+            self._log("h2d_async", ptr(p), name("pin", pinned), pinned.array.nbytes if nbytes is None else int(nbytes))
+
+        def d2h_async(self, pinned, p, nbytes):
+            assert int(nbytes) <= pinned.array.nbytes
+            self._log("d2h_async", name("pin", pinned), ptr(p), int(nbytes))
+
+        def sync(self):
+            self._log("sync")
+
+        def wait_for(self, other):
+            self._log("wait_for", other.name)
+
+        def close(self):
+            self._log("close")
+
+        class pinned_array:
+            def __init__(self, shape, dtype=np.float32):
+                self.shape, self.array, self.ptr = tuple(shape), np.zeros(shape, dtype), 1
+                Shared.tally["pinned", "host", self.array.nbytes] += 1
+
+            def close(self):
+                Shared.tally["pinned_close", "host", self.array.nbytes] += 1
+                self.array = None
+
+        def event_create(self):
+            Shared.tally["event_create", self.name] += 1
+            return Event()
+
+        def event_record(self, ev):
+            self._log("event_record", name("ev", ev))
+
+        def event_wait(self, ev):
+            self._log("event_wait", name("ev", ev))
+
+        @staticmethod
+        def event_sync(ev):
+            Shared.log.append(["event_sync", "host", name("ev", ev)])
+
+        @staticmethod
+        def event_destroy(ev):
+            Shared.tally["event_destroy"] += 1
+
+    return TraceDevice
+
+
+class TraceEngine:
+    """what texture_heightmap, generate_terrain and a TerrainWorld read of a GanStep: one context and ops per lane, and forward
+    plans whose input and output are DevTensors of the right shapes and whose programs log one row per run.
+    ``unet`` = (tile, in channels, out channels) of the pix2pix generator."""
+
+    class _Plan:
+        def __init__(self, inp, out):
+            self.input_nodes, self.out = [type("Node", (), {"out": inp})()], out
+
+    def __init__(self, unet=None):
+        from gan_heightmaps_amd.step_build import LANE_OF
+        self.Device = trace_device_class()
+        TraceEngine.current = self
+        self.devs = [self.Device(0) for _ in range(max(LANE_OF.values()) + 1)]
+        self.ops = [self.Device.ops_class(d) for d in self.devs]
+        self.lane_of, self.unet, self.param_version, self._plans = LANE_OF, unet, 0, {}
+
+    log = property(lambda self: self.Device.shared.log)
+    tally = property(lambda self: self.Device.shared.tally)
+
+    def sync(self):
+        self.log.append(["engine_sync", "host"])
+
+    def _plan(self, k, lane, in_shape, out_shape):
+        if k not in self._plans:
+            dev, ops = self.devs[lane], self.ops[lane]
+            label = "/".join(str(v) for v in k)
+            self._plans[k] = (self._Plan(dev.empty(in_shape), dev.empty(out_shape)), [(label, lambda: ops.forward(label))])
+        return self._plans[k]
+
+    def _infer_plan(self, key, B, deterministic):
+        T, c_in, c_out = self.unet
+        return self._plan((key, B, deterministic), self.lane_of[key], (B, c_in, T, T), (B, c_out, T, T))
+
+    def _subgraph_plan(self, key, tag, B, build):
+        from gan_heightmaps_amd import layers as L
+        out = build()
+        shapes = [tuple(B if v is None else v for v in l.output_shape) for l in (L.get_all_layers(out)[0], out)]
+        return self._plan((key,) + tuple(tag) + (B,), self.lane_of[key], *shapes)

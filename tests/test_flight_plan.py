@@ -148,7 +148,7 @@ def test_cli_window_mb_arguments():
 def test_cli_dispatches_a_windowed_path_to_flight(tmp_path, monkeypatch):
     """main() with --window-mb renders through TerrainWorld.flight with the path's cameras and the window size, and writes
     the frames it yields; without it, through one union scene as before"""
-    from gan_heightmaps_amd import experiments, terrain
+    from gan_heightmaps_amd import experiments, util
     calls, saved = [], []
 
     class Dev:
@@ -184,7 +184,7 @@ def test_cli_dispatches_a_windowed_path_to_flight(tmp_path, monkeypatch):
             return World()
 
     monkeypatch.setattr(experiments, "make_model", lambda name, **kw: Model())
-    monkeypatch.setattr(terrain, "_save_png", lambda name, img: saved.append((name, img)))
+    monkeypatch.setattr(util, "save_png", lambda name, img: saved.append((name, img)))
     out = str(tmp_path / "o.png")
     args = [out] + WORLD_ARGS[1:] + ["--frames", "3", "--to", "400,64,50", "--height-scale", "10", "--no-shadows"]
     assert RN.main(args + ["--window-mb", "2.5"]) == 0
