@@ -188,6 +188,9 @@ SIGNATURES = {
     "ghm_world_gather": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64],
     "ghm_render_maxmip": [_p, _p, _i32, _i32, _p, _i64],
     "ghm_render_view": [_p, C.POINTER(RenderParams), _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],
+    "ghm_render_view_sky": [_p, C.POINTER(RenderParams), _p, _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],
+    "ghm_skylight_bake": [_p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _i32, _i32, _p,
+                          _i32],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -237,6 +240,7 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_split_dgrad_dact_supported": ([_D], C.c_int),
             "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64),
             "ghm_erosion_tile": ([_i32], C.c_int32),
+            "ghm_skylight_lds_bytes": ([_i32], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

@@ -135,10 +135,12 @@ __device__ __forceinline__ bool ren_skip(const RView& v, const float* __restrict
     return fminf(za, zb) > v.hs * (m + REN_MARGIN);
 }
 
+// one pixel of one image.  sky (or null): the baked light of the sky, fp32 [H, W] (csrc/skylight.hip): the
+// ambient term of a hit becomes ambient * bilinear(sky)
 template <int TW, int TH>
-__global__ __launch_bounds__(256) void ren_view_kernel(const RView v, const float* __restrict__ hm,
-                                                       const float* __restrict__ tex, const float* __restrict__ mip,
-                                                       void* __restrict__ out, float* __restrict__ depth) {
+__device__ __forceinline__ void ren_view_pixel(const RView& v, const float* __restrict__ hm, const float* __restrict__ tex,
+                                               const float* __restrict__ mip, const float* __restrict__ sky,
+                                               void* __restrict__ out, float* __restrict__ depth) {
     __shared__ uint32_t s_off[REN_MAX_LEVELS];
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -224,7 +226,8 @@ __global__ __launch_bounds__(256) void ren_view_kernel(const RView v, const floa
             }
             if (lo < INFINITY) shadow = fminf(fmaxf(v.softness * lo, 0.0f), 1.0f);
         }
-        const float shade = v.ambient + (1.0f - v.ambient) * fmaxf(ndots, 0.0f) * shadow;
+        const float amb = sky ? v.ambient * ren_bil(sky, v.H, v.W, qy, qx) : v.ambient;
+        const float shade = amb + (1.0f - v.ambient) * fmaxf(ndots, 0.0f) * shadow;
         const float fog = 1.0f - expf(-v.haze * t_hit);
         const long plane = (long)v.H * v.W;
 #pragma unroll
@@ -249,6 +252,21 @@ __global__ __launch_bounds__(256) void ren_view_kernel(const RView v, const floa
 #pragma unroll
         for (int c = 0; c < 3; ++c) of[c * img + pix] = col[c];
     }
+}
+
+template <int TW, int TH>
+__global__ __launch_bounds__(256) void ren_view_kernel(const RView v, const float* __restrict__ hm,
+                                                       const float* __restrict__ tex, const float* __restrict__ mip,
+                                                       void* __restrict__ out, float* __restrict__ depth) {
+    ren_view_pixel<TW, TH>(v, hm, tex, mip, nullptr, out, depth);
+}
+
+template <int TW, int TH>
+__global__ __launch_bounds__(256) void ren_view_sky_kernel(const RView v, const float* __restrict__ hm,
+                                                           const float* __restrict__ tex, const float* __restrict__ mip,
+                                                           const float* __restrict__ sky, void* __restrict__ out,
+                                                           float* __restrict__ depth) {
+    ren_view_pixel<TW, TH>(v, hm, tex, mip, sky, out, depth);
 }
 
 inline bool fin(double x) { return std::isfinite(x); }
@@ -282,8 +300,8 @@ int ghm_render_maxmip(ghm_ctx* ctx, const float* hm, int32_t H, int32_t W, float
     return 0;
 }
 
-int ghm_render_view(ghm_ctx* ctx, const ghm_render_params* p, const float* hm, const float* tex, int32_t H, int32_t W,
-                    const float* mip, int32_t mip_H, int32_t mip_W, void* out, float* depth) {
+int ghm_render_view_sky(ghm_ctx* ctx, const ghm_render_params* p, const float* hm, const float* tex, const float* sky,
+                        int32_t H, int32_t W, const float* mip, int32_t mip_H, int32_t mip_W, void* out, float* depth) {
     GHM_CHECK(p && hm && tex && out, "ghm_render_view: null pointer");
     GHM_CHECK(H >= 2 && W >= 2 && (int64_t)H * W < ((int64_t)1 << 31), "ghm_render_view: scene %d x %d out of range", H, W);
     GHM_CHECK(p->Hi >= 1 && p->Wi >= 1 && (int64_t)p->Hi * p->Wi < ((int64_t)1 << 31),
@@ -342,19 +360,32 @@ int ghm_render_view(ghm_ctx* ctx, const ghm_render_params* p, const float* hm, c
     // TUNING: GHM_RENDER_TILE=16x4 | 4x16 | 8x8 -- the rectangle of pixels one wave owns
     const char* tile = GHM_OPT("GHM_RENDER_TILE");
     const std::string ts = tile ? tile : "8x8";
+    // a scene without a sky plane runs the kernel it always ran
+#define REN_LAUNCH(TW, TH)                                                                                                   \
+    do {                                                                                                                     \
+        const dim3 grid(ceil_div(v.Wi, 2 * TW), ceil_div(v.Hi, 2 * TH));                                                     \
+        if (sky)                                                                                                             \
+            hipLaunchKernelGGL((ren_view_sky_kernel<TW, TH>), grid, dim3(256), 0, ctx->stream, v, hm, tex, mip, sky, out,    \
+                               depth);                                                                                       \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((ren_view_kernel<TW, TH>), grid, dim3(256), 0, ctx->stream, v, hm, tex, mip, out, depth);     \
+    } while (0)
     if (ts == "16x4") {
-        hipLaunchKernelGGL((ren_view_kernel<16, 4>), dim3(ceil_div(v.Wi, 32), ceil_div(v.Hi, 8)), dim3(256), 0, ctx->stream, v,
-                           hm, tex, mip, out, depth);
+        REN_LAUNCH(16, 4);
     } else if (ts == "4x16") {
-        hipLaunchKernelGGL((ren_view_kernel<4, 16>), dim3(ceil_div(v.Wi, 8), ceil_div(v.Hi, 32)), dim3(256), 0, ctx->stream, v,
-                           hm, tex, mip, out, depth);
+        REN_LAUNCH(4, 16);
     } else {
         GHM_CHECK(ts == "8x8", "ghm_render_view: GHM_RENDER_TILE=%s (8x8, 16x4 or 4x16)", ts.c_str());
-        hipLaunchKernelGGL((ren_view_kernel<8, 8>), dim3(ceil_div(v.Wi, 16), ceil_div(v.Hi, 16)), dim3(256), 0, ctx->stream, v,
-                           hm, tex, mip, out, depth);
+        REN_LAUNCH(8, 8);
     }
+#undef REN_LAUNCH
     GHM_LAUNCH_CHECK();
     return 0;
+}
+
+int ghm_render_view(ghm_ctx* ctx, const ghm_render_params* p, const float* hm, const float* tex, int32_t H, int32_t W,
+                    const float* mip, int32_t mip_H, int32_t mip_W, void* out, float* depth) {
+    return ghm_render_view_sky(ctx, p, hm, tex, nullptr, H, W, mip, mip_H, mip_W, out, depth);
 }
 
 }  // extern "C"

@@ -1142,6 +1142,45 @@ class Ops:
              int(W), _vp(mip.ptr if mip is not None else None), mip.H if mip is not None else 0,
              mip.W if mip is not None else 0, _vp(out_ptr), _vp(depth_ptr))
 
+    def render_view_sky(self, params, hm_ptr, tex_ptr, sky_ptr, H, W, mip, out_ptr, depth_ptr=None):
+        """render_view with the baked light of the sky: sky_ptr is a fp32 [H, W] plane (skylight_bake's), and a hit's
+        ambient term becomes ambient * bilinear(sky); None gives render_view's bits"""
+        call("ghm_render_view_sky", self.h, C.byref(params) if params is not None else None, _vp(hm_ptr), _vp(tex_ptr),
+             _vp(sky_ptr), int(H), int(W), _vp(mip.ptr if mip is not None else None), mip.H if mip is not None else 0,
+             mip.W if mip is not None else 0, _vp(out_ptr), _vp(depth_ptr))
+
+    # the light of the sky (csrc/skylight.hip, gan_heightmaps_amd/skylight.py)
+    SKY_TABLES = 8                 # tables a context keeps (a table is at most 64 x 256 x 20 bytes)
+
+    @staticmethod
+    def skylight_lds_bytes(reach):
+        """bytes of LDS a block of the tiled form needs for this reach, or -1 where the form is refused"""
+        return int(_lib.load().ghm_skylight_lds_bytes(int(reach)))
+
+    def skylight_table(self, sky):
+        """the device copy of ``sky.table()`` (a skylight.SkyLight): uploaded once per SkyLight and context, freed with the
+        context (the least recently used leaves when more than SKY_TABLES are alive)"""
+        cache = self.dev.__dict__.setdefault("_sky_tables", {})
+        ptr = cache.pop(sky, None)
+        if ptr is None:
+            tab = np.ascontiguousarray(sky.table())
+            ptr = self.dev.alloc(tab.nbytes)
+            self.dev.h2d(ptr, tab)
+            while len(cache) >= self.SKY_TABLES:
+                self.dev.sync()
+                self.dev.free(cache.pop(next(iter(cache))))
+        cache[sky] = ptr
+        return ptr
+
+    def skylight_bake(self, src_ptr, rows, cols, pitch, table_ptr, directions, steps, reach, y0, x0, h, w, height_scale,
+                      strength, tiled, out_u8, out_ptr, out_pitch):
+        """the sky light of the texels [y0, y0 + h) x [x0, x0 + w) of the fp32 plane at src_ptr (rows x cols, rows of
+        ``pitch`` cells; indices are clamped to it) -> out_ptr (rows of out_pitch cells), fp32 or uint8.  table_ptr:
+        skylight_table(); reach: the table's"""
+        call("ghm_skylight_bake", self.h, _vp(src_ptr), int(rows), int(cols), int(pitch), _vp(table_ptr), int(directions),
+             int(steps), int(reach), int(y0), int(x0), int(h), int(w), float(height_scale), float(strength), int(bool(tiled)),
+             int(bool(out_u8)), _vp(out_ptr), int(out_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

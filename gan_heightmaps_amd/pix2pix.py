@@ -176,15 +176,26 @@ class Pix2Pix:
         self.engine.sync()
         return erode(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, erosion, **kw)
 
-    def render_terrain(self, heightmap, texture, camera, height_scale=None, **kw):
+    def sky_visibility(self, heightmap, sky=None, **kw):
+        """The light of the sky on a heightmap, a horizon scan baked on the GPU (gan_heightmaps_amd/skylight.py, DESIGN
+        §4r).  Not in the reference.  heightmap: (H, W), floating point in [0, 1] or uint8; sky: a skylight.SkyLight (default
+        SkyLight()); kw: bake's (height_scale, margin, out, uint8, tiled).  Returns the (H, W) plane, float32 in [0, 1]: 1
+        where the whole sky is seen.  Leaves the training state untouched."""
+        from .skylight import bake
+        from .step import LANE_OF
+        self.engine.sync()
+        return bake(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, sky, **kw)
+
+    def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in
-        the heightmap's pixel coordinates; kw: Scene.render's (sun, shadows, haze, step, max_dist, uint8, out, accel).
+        the heightmap's pixel coordinates; sky: a skylight.SkyLight, the scene is lit from the sky; kw:
+        Scene.render's (sun, shadows, haze, step, max_dist, uint8, out, accel).
         For many frames of one terrain build a render.Scene once instead.  Leaves the training state untouched."""
         from .render import DEFAULTS, Scene
         self.engine.sync()
         with Scene(heightmap, texture, height_scale=DEFAULTS['height_scale'] if height_scale is None else height_scale,
-                   value_range=(self.is_a_grayscale, self.is_b_grayscale), device=self.device) as scene:
+                   value_range=(self.is_a_grayscale, self.is_b_grayscale), device=self.device, sky=sky) as scene:
             return scene.render(camera, **kw)
 
     # ---- sliced Wasserstein distance of the generators (gan_heightmaps_amd/swd.py, DESIGN §4q) ------------------------

@@ -5,7 +5,9 @@
     camera  position (y, x, z), yaw, pitch (negative looks down), vertical field of view, image size.
             forward = (cos p cos w, cos p sin w, sin p), right = (sin w, -cos w, 0), up = (-sin p cos w, -sin p sin w, cos p).
     march   samples at t_k = k step; the first sample at or below the surface is the hit, refined by one secant step.
-    colour  texture x (ambient + (1 - ambient) max(0, n.s) shadow), then haze towards the sky colour.
+    colour  texture x (ambient + (1 - ambient) max(0, n.s) shadow), then haze towards the sky colour.  A scene built with
+            ``sky=SkyLight(...)`` bakes the light of the sky once (skylight.py) and shades with
+            ambient x bilinear(sky plane) in place of ambient.
 
 A ``Scene`` uploads the two arrays once and builds the maximum pyramid once; every ``render`` after that is one launch and one
 download.  ``Pix2Pix.render_terrain`` renders arrays the caller has, ``TerrainWorld.scene`` / ``TerrainWorld.view`` render the
@@ -15,7 +17,7 @@ unbounded world (the scene is assembled through the host: ``both`` -> upload; ``
     python -m gan_heightmaps_amd.render OUT.png (--heightmap F --texture F | --world EXPERIMENT MODEL --seed N
         [--chunk-cells C] [--blend B] [--dtype D] [--erode N]) --pos Y,X,Z (--look-at Y,X,Z | --yaw A --pitch A) [--fov DEG]
         [--size HxW] [--max-dist N] [--height-scale S] [--sun AZ,EL] [--no-shadows] [--haze V] [--step V]
-        [--frames N --to Y,X,Z [--window-mb M]]
+        [--frames N --to Y,X,Z [--window-mb M]] [--sky [--sky-directions N] [--sky-steps N] [--sky-step X] [--sky-strength X]]
 """
 import argparse
 import math
@@ -143,6 +145,15 @@ def _unit_planes(a, grey, what):
     raise ValueError("%s must be uint8 (H, W) / (H, W, C) or float32 (H, W) / (C, H, W), got %s %s" % (what, a.dtype, a.shape))
 
 
+def _check_sky(sky, margin):
+    from .skylight import SkyLight
+    if sky is not None and not isinstance(sky, SkyLight):
+        raise ValueError("sky must be a skylight.SkyLight, got %r" % (sky,))
+    if not _is_int(margin) or margin < 0:
+        raise ValueError("margin must be an integer >= 0, got %r" % (margin,))
+    return sky, int(margin)
+
+
 class Scene:
     """A heightmap and its texture resident on the GPU, ready to be looked at.
 
@@ -150,10 +161,13 @@ class Scene:
     value_range: (heightmap_is_unit, texture_is_unit) -- the model's (is_a_grayscale, is_b_grayscale): True means the float
     values are already in [0, 1], False the tanh range; None takes one-channel arrays as unit and three-channel ones as tanh.
     A three-channel heightmap gives the mean of its channels as height; a one-channel texture is replicated.
-    origin: the world coordinates (Y0, X0) of the scene's first pixel; cameras are given in world coordinates."""
+    origin: the world coordinates (Y0, X0) of the scene's first pixel; cameras are given in world coordinates.
+    sky: a skylight.SkyLight: the scene bakes the light of the sky once, after the pyramid, and every render shades with it
+    (DESIGN §4r).  margin = m > 0: the heightmap is (H + 2m, W + 2m), the texture (H, W), and the scene is the interior; the
+    apron feeds the bake alone (m = sky.reach makes the plane independent of the scene's borders) and is freed after it."""
 
     def __init__(self, heightmap, texture, origin=(0, 0), height_scale=DEFAULTS['height_scale'], value_range=None,
-                 device=None):
+                 device=None, sky=None, margin=0):
         if len(tuple(origin)) != 2 or not all(_is_int(v) for v in origin):
             raise ValueError("origin must be two integers (Y0, X0), got %r" % (origin,))
         if not _num(height_scale) or height_scale <= 0:
@@ -169,6 +183,12 @@ class Scene:
         tex = _unit_planes(texture, grey(texture, tg), "texture")
         hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
         tex = np.ascontiguousarray(np.broadcast_to(tex, (3,) + tex.shape[1:]))
+        sky, margin = _check_sky(sky, margin)
+        grown = hm
+        if margin:
+            if hm.shape[0] <= 2 * margin or hm.shape[1] <= 2 * margin:
+                raise ValueError("a heightmap of %s has no interior inside a margin of %d" % (hm.shape, margin))
+            hm = np.ascontiguousarray(hm[margin:-margin, margin:-margin])
         if hm.shape != tex.shape[1:]:
             raise ValueError("heightmap %s and texture %s differ in size" % (hm.shape, tex.shape[1:]))
         H, W = hm.shape
@@ -181,28 +201,44 @@ class Scene:
         self._own = device is None
         self.dev = Device(int(os.environ.get("LOCAL_RANK", "0"))) if device is None else device
         self.ops = Ops(self.dev)
-        self._hm = self._tex = self._mip = None
+        self._hm = self._tex = self._mip = self._sky = None
         self._outbuf, self._outbytes = None, 0
+        self.sky = sky
+        src = None
         try:
             self._hm = self.dev.alloc(hm.nbytes)
             self.dev.h2d(self._hm, hm)
             self._tex = self.dev.alloc(tex.nbytes)
             self.dev.h2d(self._tex, tex)
             self._mip = self.ops.render_maxmip(self._hm, H, W)
+            if sky is not None and margin:
+                src = self.dev.alloc(grown.nbytes)
+                self.dev.h2d(src, grown)
+            src = self._bake_sky(src, margin)
         except Exception:
+            if src:
+                self.dev.free(src)
             self.close()
             raise
 
     @classmethod
-    def from_device(cls, dev, hm_ptr, tex_ptr, H, W, origin=(0, 0), height_scale=DEFAULTS['height_scale']):
+    def from_device(cls, dev, hm_ptr, tex_ptr, H, W, origin=(0, 0), height_scale=DEFAULTS['height_scale'], sky=None,
+                    sky_src=None, margin=0):
         """a Scene over two buffers that are already on ``dev`` and already hold what the constructor would upload: hm fp32
         [H, W] in [0, 1] and tex fp32 [3, H, W] in [0, 1], both allocated with dev.alloc.  The scene takes ownership of them
-        (close() frees them, and so does a failure in here); nothing is uploaded, the pyramid is built as usual."""
+        (close() frees them, and so does a failure in here); nothing is uploaded, the pyramid is built as usual.
+        sky: a skylight.SkyLight, baked after the pyramid from sky_src: the height plane grown by ``margin`` all round, fp32
+        [H + 2 margin, W + 2 margin] from dev.alloc, owned in the same way and freed after the bake (None with margin = 0:
+        the bake reads hm itself)."""
         self = cls.__new__(cls)
         self.dev, self._own = dev, False
-        self._hm, self._tex, self._mip = hm_ptr, tex_ptr, None
+        self._hm, self._tex, self._mip, self._sky = hm_ptr, tex_ptr, None, None
         self._outbuf, self._outbytes = None, 0
+        self.sky = None
         try:
+            self.sky, margin = _check_sky(sky, margin)
+            if (sky_src is not None) != (self.sky is not None and margin > 0):
+                raise ValueError("sky_src is the grown height plane of a scene with sky and margin > 0, and of no other")
             if len(tuple(origin)) != 2 or not all(_is_int(v) for v in origin):
                 raise ValueError("origin must be two integers (Y0, X0), got %r" % (origin,))
             if not _num(height_scale) or height_scale <= 0:
@@ -217,10 +253,39 @@ class Scene:
             self.shape = (int(H), int(W))
             self.ops = Ops(dev)
             self._mip = self.ops.render_maxmip(self._hm, self.shape[0], self.shape[1])
+            sky_src = self._bake_sky(sky_src, margin)
         except Exception:
+            if sky_src:
+                dev.sync()
+                dev.free(sky_src)
             self.close()
             raise
         return self
+
+    def _bake_sky(self, src, margin):
+        """bake the scene's sky plane from ``src`` (the height plane grown by ``margin``, freed here; None: the scene's own
+        plane); returns None, the pointer the caller still owns"""
+        if self.sky is None:
+            return None
+        from .skylight import bake_device
+        H, W = self.shape
+        self._sky = self.dev.alloc(4 * H * W)
+        bake_device(self.ops, src if src else self._hm, H + 2 * margin, W + 2 * margin, self.sky, self.height_scale,
+                    self._sky, margin=margin)
+        if src:
+            self.dev.sync()
+            self.dev.free(src)
+        return None
+
+    def sky_plane(self):
+        """the baked light of the sky, downloaded: float32 [H, W] in [0, 1]"""
+        if self.dev is None:
+            raise ValueError("this Scene is closed")
+        if self._sky is None:
+            raise ValueError("this Scene was built without sky=")
+        out = np.empty(self.shape, np.float32)
+        self.dev.d2h(out, self._sky, out.nbytes)
+        return out
 
     def arrays(self):
         """the scene's planes as the renderer reads them, downloaded: (hm [H, W], tex [3, H, W]), float32 in [0, 1]"""
@@ -245,12 +310,12 @@ class Scene:
             return
         if dev.h is not None:
             dev.sync()
-            for p in (self._hm, self._tex, self._mip.ptr if self._mip else None, self._outbuf):
+            for p in (self._hm, self._tex, self._mip.ptr if self._mip else None, self._sky, self._outbuf):
                 if p:
                     dev.free(p)
             if self._own:
                 dev.close()
-        self._hm = self._tex = self._mip = self._outbuf = None
+        self._hm = self._tex = self._mip = self._sky = self._outbuf = None
         self.dev = None
 
     def default_max_dist(self, camera):
@@ -305,7 +370,10 @@ class Scene:
             self._outbuf, self._outbytes = self.dev.alloc(need), need
         H, W = self.shape
         dptr = self._outbuf + (out.nbytes + 15) // 16 * 16 if depth is not None else None
-        self.ops.render_view(p, self._hm, self._tex, H, W, self._mip, self._outbuf, dptr)
+        if self._sky is None:
+            self.ops.render_view(p, self._hm, self._tex, H, W, self._mip, self._outbuf, dptr)
+        else:
+            self.ops.render_view_sky(p, self._hm, self._tex, self._sky, H, W, self._mip, self._outbuf, dptr)
         self.dev.d2h(out, self._outbuf, out.nbytes)
         if depth is not None:
             self.dev.d2h(depth, dptr, depth.nbytes)
@@ -377,6 +445,12 @@ def parse_args(argv):
     p.add_argument("--window-mb", type=float, default=None, metavar="M",
                    help="with --world and --frames: render the path through TerrainWorld.flight, from scene windows of at "
                         "most M MiB built on the device one after the other (default: one scene over the whole path)")
+    p.add_argument("--sky", action="store_true", help="light the ground from the sky: bake a horizon scan per scene "
+                                                      "(gan_heightmaps_amd.skylight) and dim the ambient light by it")
+    p.add_argument("--sky-directions", type=int, default=None, help="azimuths of the scan (with --sky)")
+    p.add_argument("--sky-steps", type=int, default=None, help="samples per azimuth (with --sky)")
+    p.add_argument("--sky-step", type=float, default=None, help="pixels between samples (with --sky)")
+    p.add_argument("--sky-strength", type=float, default=None, help="how far the visibility dims the light, in [0, 1]")
     # a value that starts with a minus sign would read as an option: hand it over in the --opt=value form
     argv = list(argv)
     i = 0
@@ -426,6 +500,16 @@ def parse_args(argv):
         p.error("--window-mb must be > 0")
     if not a.output.endswith(".png"):
         p.error("the output must be a .png")
+    skw = {k: getattr(a, "sky_" + k) for k in ("directions", "steps", "step", "strength") if getattr(a, "sky_" + k) is not None}
+    if skw and not a.sky:
+        p.error("--sky-directions / --sky-steps / --sky-step / --sky-strength need --sky")
+    a.skylight = None
+    if a.sky:
+        from .skylight import SkyLight
+        try:
+            a.skylight = SkyLight(**skw)
+        except ValueError as e:
+            p.error(str(e))
     return a
 
 
@@ -470,13 +554,15 @@ def main(argv=None):
                 # a window after the other, each built on the device: memory does not grow with the path
                 fkw = {k: v for k, v in kw.items() if k != "max_dist"}
                 for name, img in zip(frame_names(a), world.flight(cams, a.max_dist, window_mb=a.window_mb,
-                                                                  height_scale=a.height_scale, **fkw)):
+                                                                  height_scale=a.height_scale, sky=a.skylight, **fkw)):
                     util.save_png(name, img)
                 return 0
             # one scene over the union of the frames' footprints
-            scene = world.scene(*union_footprint([c.footprint(a.max_dist) for c in cams]), height_scale=a.height_scale)
+            scene = world.scene(*union_footprint([c.footprint(a.max_dist) for c in cams]), height_scale=a.height_scale,
+                                sky=a.skylight)
         else:
-            scene = Scene(util.read_image(a.heightmap), util.read_image(a.texture), height_scale=a.height_scale)
+            scene = Scene(util.read_image(a.heightmap), util.read_image(a.texture), height_scale=a.height_scale,
+                          sky=a.skylight)
         for cam, name in zip(cams, frame_names(a)):
             util.save_png(name, scene.render(cam, **kw))
     finally:

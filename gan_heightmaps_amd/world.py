@@ -42,6 +42,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import erosion as _erosion
+from . import skylight as _skylight
 from . import layers as L
 from .streaming import DownloadRing, check_uint8_channels, output_array, shift_accumulator, store_rows
 from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
@@ -49,7 +50,7 @@ from . import terrain as _terrain
 from .texture import check_overlap
 from .util import is_int as _is_int
 
-__all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
+__all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "SKY_SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
            "window_elements", "default_chunk_cells", "slot_batches", "erosion_sources", "snap_out", "plan_windows", "TerrainWorld",
            "parse_region",
            "parse_args", "main"]
@@ -134,6 +135,14 @@ def erosion_sources(a, b, K, E):
 # bytes of device memory a render scene keeps per pixel: the height plane (4), the three texture planes (12) and
 # the maximum pyramid (4/3 of the map, 16/3 bytes), rounded up
 SCENE_BYTES_PER_PIXEL = 22
+# a scene lit from the sky keeps its baked plane too (4)
+SKY_SCENE_BYTES_PER_PIXEL = SCENE_BYTES_PER_PIXEL + 4
+
+
+def _check_sky(sky):
+    if sky is not None and not isinstance(sky, _skylight.SkyLight):
+        raise ValueError("sky must be a skylight.SkyLight, got %r" % (sky,))
+    return sky
 
 
 def snap_out(rect, snap):
@@ -605,20 +614,31 @@ class TerrainWorld:
         """(heightmap, texture) of one rectangle from one pass over the chunks; bit for bit the two separate calls"""
         return self._request(y0, x0, h, w, True, True, out_heightmap, out_texture, uint8, uint8)
 
-    def scene(self, y0, x0, h, w, resident=False, **kw):
+    def scene(self, y0, x0, h, w, resident=False, sky=None, **kw):
         """the rectangle as a render.Scene with origin (y0, x0): ``both`` in float32, uploaded once.  Cameras are
         given in world coordinates.  kw: height_scale.  Close it, or use it as a context manager.
         resident=True assembles the same scene on the device: the chunks' and the accumulator's rows are mapped
         and written straight into the scene's planes, nothing visits the host; the planes, and so every render, are bit for
-        bit the default's."""
+        bit the default's.
+        sky: a skylight.SkyLight: the scene is lit from the sky.  Its plane is baked from the heights of the
+        rectangle grown by sky.reach all round (``heightmap`` of the grown rectangle; resident: a heightmap-only request into
+        a transient device plane), from the same chunks, so the baked value of a world pixel does not depend on the scene
+        that contains it."""
         from .render import Scene
+        sky = _check_sky(sky)
         if resident:
-            return self._resident_scene(y0, x0, h, w, **kw)
-        hm, tex = self.both(y0, x0, h, w)
+            return self._resident_scene(y0, x0, h, w, sky=sky, **kw)
+        if sky is None:
+            hm, tex = self.both(y0, x0, h, w)
+            margin = 0
+        else:
+            margin = sky.reach
+            hm = self.heightmap(y0 - margin, x0 - margin, h + 2 * margin, w + 2 * margin)
+            tex = self.texture(y0, x0, h, w)
         return Scene(hm, tex, origin=(y0, x0), value_range=(self.model.is_a_grayscale, self.model.is_b_grayscale),
-                     device=self.model.device, **kw)
+                     device=self.model.device, sky=sky, margin=margin, **kw)
 
-    def _resident_scene(self, y0, x0, h, w, **kw):
+    def _resident_scene(self, y0, x0, h, w, sky=None, **kw):
         from .render import Scene
         y0, x0, h, w = self._check_region(y0, x0, h, w)
         if h < 2 or w < 2 or h * w >= 1 << 31:
@@ -626,6 +646,7 @@ class TerrainWorld:
         if self._closed:
             raise ValueError("this TerrainWorld is closed")
         dev = self.model.device
+        margin = 0 if sky is None else sky.reach
         bufs = []
         try:
             for n in (4 * h * w, 12 * h * w, 4):                  # the height plane, the three texture planes, the flag
@@ -633,6 +654,16 @@ class TerrainWorld:
             hm, tex, flag = bufs
             dev.memset_zero(flag, 4)
             dev.sync()
+            grown = None
+            if sky is not None:
+                # the height plane of the grown rectangle: the same chunks, mapped as the scene's own plane is
+                gh, gw = h + 2 * margin, w + 2 * margin
+                if gh * gw >= 1 << 31:
+                    raise ValueError("the scene grown by the sky's reach, %d x %d, is beyond 2^31 pixels" % (gh, gw))
+                grown = dev.alloc(4 * gh * gw)
+                bufs.append(grown)
+                self._request(y0 - margin, x0 - margin, gh, gw, True, False, None, None, False, False,
+                              scene=(grown, None, flag))
             self._request(y0, x0, h, w, True, True, None, None, False, False, scene=(hm, tex, flag))
             seen = np.zeros(1, np.int32)
             dev.d2h(seen, flag, 4)
@@ -643,47 +674,54 @@ class TerrainWorld:
                 dev.free(p)
             raise
         dev.free(flag)
-        return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), **kw)
+        return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), sky=sky, sky_src=grown, margin=margin, **kw)
 
-    def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None):
+    def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
         consecutive frames i .. j such that the union of their footprints, expanded outward to multiples of ``snap``
         (default in_shp), has at most max_pixels = floor(window_mb 2^20 / 22) pixels: a scene keeps 22 bytes per pixel
         (SCENE_BYTES_PER_PIXEL: 4 of height, 12 of texture, 16/3 of pyramid, rounded up).  The next window starts at j + 1.  A
-        frame whose own snapped footprint exceeds the cap is a ValueError.  Deterministic in its arguments alone."""
+        frame whose own snapped footprint exceeds the cap is a ValueError.  Deterministic in its arguments alone.
+        sky: a skylight.SkyLight: the windows are lit from the sky and planned with 26 bytes per pixel
+        (SKY_SCENE_BYTES_PER_PIXEL: the 22 and the baked plane's 4).  The height plane grown by sky.reach that a window's bake
+        reads is transient -- allocated before the bake, freed after it -- and outside this budget."""
+        bpp = SCENE_BYTES_PER_PIXEL if _check_sky(sky) is None else SKY_SCENE_BYTES_PER_PIXEL
         if isinstance(window_mb, bool) or not isinstance(window_mb, (int, float, np.integer, np.floating)) \
                 or not window_mb > 0:
             raise ValueError("window_mb must be a number > 0, got %r" % (window_mb,))
         snap = self._geo.out if snap is None else snap
-        return plan_windows([c.footprint(max_dist) for c in cameras], snap,
-                            int(window_mb * (1 << 20)) // SCENE_BYTES_PER_PIXEL)
+        return plan_windows([c.footprint(max_dist) for c in cameras], snap, int(window_mb * (1 << 20)) // bpp)
 
-    def flight(self, cameras, max_dist, window_mb=1024, snap=None, height_scale=None, **render_kw):
+    def flight(self, cameras, max_dist, window_mb=1024, snap=None, height_scale=None, sky=None, **render_kw):
         """the images of a camera path of any length, one per camera and in order, from bounded device memory:
         for each window of flight_plan one resident scene is built, its frames are rendered (one launch and one download
         each), and it is closed before the next is built; chunks that consecutive windows share come from the cache.
         Frame k is bit for bit Scene(*world.both(*rect), origin=rect[:2], ...).render(cameras[k], max_dist=max_dist, ...)
         for its window's rect.  The plan is made, and its refusals raised, by this call; the device works as the returned
-        generator is consumed.  render_kw: Scene.render's."""
+        generator is consumed.  render_kw: Scene.render's.
+        sky: a skylight.SkyLight: every window is lit from the sky, and frame k is bit for bit the host-path
+        world.scene(*rect, sky=sky) rendered.  The plan counts the baked plane (flight_plan); the grown height plane of a
+        window's bake lives only while the window is built and is outside window_mb."""
         cameras = list(cameras)
         if self._closed:
             raise ValueError("this TerrainWorld is closed")
-        plan = self.flight_plan(cameras, max_dist, window_mb, snap)
+        plan = self.flight_plan(cameras, max_dist, window_mb, snap, sky=sky)
         skw = {} if height_scale is None else {"height_scale": height_scale}
 
         def frames():
             for rect, i, j in plan:
-                with self.scene(*rect, resident=True, **skw) as scene:
+                with self.scene(*rect, resident=True, sky=sky, **skw) as scene:
                     for k in range(i, j + 1):
                         yield scene.render(cameras[k], max_dist=max_dist, **render_kw)
         return frames()
 
-    def view(self, camera, max_dist, height_scale=None, **kw):
+    def view(self, camera, max_dist, height_scale=None, sky=None, **kw):
         """one image of the world from ``camera`` (world coordinates, negative ones included), rays ``max_dist`` long: the
-        scene of camera.footprint(max_dist), rendered.  kw: Scene.render's."""
+        scene of camera.footprint(max_dist), rendered.  sky: a skylight.SkyLight, the scene is lit from the sky.  kw:
+        Scene.render's."""
         skw = {} if height_scale is None else {"height_scale": height_scale}
-        with self.scene(*camera.footprint(max_dist), **skw) as scene:
+        with self.scene(*camera.footprint(max_dist), sky=sky, **skw) as scene:
             return scene.render(camera, max_dist=max_dist, **kw)
 
     def _request(self, y0, x0, h, w, want_hm, want_tex, out_hm, out_tex, hm_u8, tex_u8, scene=None):
