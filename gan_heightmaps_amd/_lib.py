@@ -191,6 +191,9 @@ SIGNATURES = {
     "ghm_render_view_sky": [_p, C.POINTER(RenderParams), _p, _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p],
     "ghm_skylight_bake": [_p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _i32, _i32, _p,
                           _i32],
+    "ghm_mesh_errors": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32],
+    "ghm_mesh_count": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, C.POINTER(_i64), C.POINTER(_i64)],
+    "ghm_mesh_extract": [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _p, _p, _i64, _i64],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -241,6 +244,7 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_render_maxmip_elems": ([_i32, _i32], C.c_int64),
             "ghm_erosion_tile": ([_i32], C.c_int32),
             "ghm_skylight_lds_bytes": ([_i32], C.c_int64),
+            "ghm_mesh_workspace": ([_i32, _i32], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

@@ -1181,6 +1181,33 @@ class Ops:
              int(steps), int(reach), int(y0), int(x0), int(h), int(w), float(height_scale), float(strength), int(bool(tiled)),
              int(bool(out_u8)), _vp(out_ptr), int(out_pitch))
 
+    # adaptive triangle meshes (csrc/mesh.hip, gan_heightmaps_amd/mesh.py)
+    @staticmethod
+    def mesh_workspace(h, w):
+        """bytes of device workspace mesh_count and mesh_extract need for a rectangle of h x w pixels, or -1"""
+        return int(_lib.load().ghm_mesh_workspace(int(h), int(w)))
+
+    def mesh_errors(self, src_ptr, rows, cols, pitch, tile_log2, fused, err_ptr, err_pitch):
+        """the error of every vertex of the fp32 height plane at src_ptr ((R T + 1) x (C T + 1), T = 2^tile_log2, rows of
+        ``pitch`` cells) -> the fp32 plane at err_ptr (rows of err_pitch cells); fused: the LDS form of the finest scales"""
+        call("ghm_mesh_errors", self.h, _vp(src_ptr), int(rows), int(cols), int(pitch), int(tile_log2), int(bool(fused)),
+             _vp(err_ptr), int(err_pitch))
+
+    def mesh_count(self, err_ptr, rows, cols, err_pitch, tile_log2, y0, x0, h, w, max_error, workspace_ptr):
+        """(vertices, triangles) of the mesh of the tiles [y0, y0 + h] x [x0, x0 + w] at max_error; waits for the stream"""
+        V, F = C.c_int64(0), C.c_int64(0)
+        call("ghm_mesh_count", self.h, _vp(err_ptr), int(rows), int(cols), int(err_pitch), int(tile_log2), int(y0), int(x0),
+             int(h), int(w), float(max_error), _vp(workspace_ptr), C.byref(V), C.byref(F))
+        return int(V.value), int(F.value)
+
+    def mesh_extract(self, src_ptr, pitch, err_ptr, rows, cols, err_pitch, tile_log2, y0, x0, h, w, max_error, workspace_ptr,
+                     index_ptr, grid_ptr, heights_ptr, triangles_ptr, vertices, triangles):
+        """the same mesh -> index int32 [(h + 1) (w + 1)], grid int32 [vertices, 2], heights fp32 [vertices], triangles
+        uint32 [triangles, 3]; the totals are mesh_count's"""
+        call("ghm_mesh_extract", self.h, _vp(src_ptr), int(pitch), _vp(err_ptr), int(rows), int(cols), int(err_pitch),
+             int(tile_log2), int(y0), int(x0), int(h), int(w), float(max_error), _vp(workspace_ptr), _vp(index_ptr),
+             _vp(grid_ptr), _vp(heights_ptr), _vp(triangles_ptr), int(vertices), int(triangles))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

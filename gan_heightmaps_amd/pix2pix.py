@@ -186,6 +186,17 @@ class Pix2Pix:
         self.engine.sync()
         return bake(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, sky, **kw)
 
+    def heightmap_mesh(self, heightmap, max_error, tile=None, fused=None):
+        """A heightmap as an adaptive triangle mesh, cut on the GPU (gan_heightmaps_amd/mesh.py).  Not in the
+        reference.  heightmap: (H, W) or (1, H, W), floating point in [0, 1] or uint8, of any size (edge-replicated to whole
+        tiles); max_error: the tolerance in height units; tile: the root square side, a power of two (None: the largest
+        <= 256 that does not exceed the shorter side); fused: mesh.ErrorMap's.  Returns a mesh.TerrainMesh (``save`` writes
+        .glb / .obj / .npz).  Leaves the training state untouched."""
+        from .mesh import heightmap_mesh
+        from .step import LANE_OF
+        self.engine.sync()
+        return heightmap_mesh(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, max_error, tile=tile, fused=fused)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

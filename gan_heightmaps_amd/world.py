@@ -35,6 +35,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
 """
 import argparse
+import os
 import re
 import sys
 from collections import OrderedDict
@@ -676,6 +677,55 @@ class TerrainWorld:
         dev.free(flag)
         return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), sky=sky, sky_src=grown, margin=margin, **kw)
 
+    def mesh(self, y0, x0, h, w, max_error, tile=256, texture=False, fused=None):
+        """the rectangle as an adaptive triangle mesh (mesh.TerrainMesh) with the (h + 1) x (w + 1) vertices
+        [y0, y0 + h] x [x0, x0 + w] and origin (y0, x0); heights in [0, 1], mapped as a scene's.  y0, x0, h, w are multiples
+        of ``tile``.  The height plane of the rectangle grown by one ring of tiles is assembled on the device (a
+        heightmap-only request into a transient plane, nothing visits the host), its error map is computed there, and the
+        extraction is restricted to the inner tiles: the errors there are those of the unbounded forest, so meshes of
+        neighbouring rectangles, made at any time, share their border vertices and edges bit for bit.  An eroded world
+        meshes as the eroded world.  texture=True: returns (mesh, self.texture(y0, x0, h + 1, w + 1, uint8=True)).
+        fused: mesh.ErrorMap's."""
+        from . import mesh as _mesh
+        _mesh._tile_log2(tile)
+        tol = _mesh._check_error(max_error)
+        tile = int(tile)
+        for name, v in (("y0", y0), ("x0", x0), ("h", h), ("w", w)):
+            if not _is_int(v) or v % tile:
+                raise ValueError("%s must be a multiple of the tile (%d), got %r" % (name, tile, v))
+        if h < tile or w < tile:
+            raise ValueError("the region must be at least one tile (%d) each way, got %d x %d" % (tile, h, w))
+        if self._closed:
+            raise ValueError("this TerrainWorld is closed")
+        gh, gw = h + 2 * tile + 1, w + 2 * tile + 1
+        if gh * gw >= 1 << 31:
+            raise ValueError("the region grown by a ring of tiles, %d x %d, is at or beyond 2^31 vertices" % (gh, gw))
+        gy, gx, gh, gw = self._check_region(y0 - tile, x0 - tile, gh, gw)
+        self._bind()
+        dev = self._dev
+        bufs = []
+        try:
+            for n in (4 * gh * gw, 4):
+                bufs.append(dev.alloc(n))
+            grown, flag = bufs
+            dev.memset_zero(flag, 4)
+            dev.sync()
+            self._request(gy, gx, gh, gw, True, False, None, None, False, False, scene=(grown, None, flag))
+            seen = np.zeros(1, np.int32)
+            dev.d2h(seen, flag, 4)
+            if seen[0]:
+                raise ValueError("the heightmap has non-finite values")
+            with _mesh.ErrorMap(self._ops, _mesh.DevicePlane(grown, gh, gw), tile=tile, fused=fused, origin=(gy, gx),
+                                own=False) as em:
+                m = em.extract(tol, rect=(tile, tile, int(h), int(w)))
+        finally:
+            dev.sync()
+            for p_ in bufs:
+                dev.free(p_)
+        if texture:
+            return m, self.texture(int(y0), int(x0), int(h) + 1, int(w) + 1, uint8=True)
+        return m
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -854,6 +904,14 @@ def parse_args(argv):
     p.add_argument("--erode", type=int, default=None, metavar="N",
                    help="erode the world with N iterations of the water simulation (erosion.Erosion's other defaults); "
                         "part of the world's identity")
+    p.add_argument("--mesh", default=None, metavar="OUT_MESH",
+                   help="also write the region as an adaptive triangle mesh: .glb, .obj or .npz, with the (H + 1) x (W + 1) "
+                        "vertices [Y0, Y0 + H] x [X0, X0 + W]; the region must be made of whole tiles; with --texture the "
+                        "mesh carries the texture")
+    p.add_argument("--max-error", type=float, default=None, metavar="E",
+                   help="the mesh's tolerance in height units (heights are in [0, 1]; default 0.01)")
+    p.add_argument("--tile", type=int, default=None, metavar="T",
+                   help="the mesh's root square side, a power of two (default 256)")
     # a region that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i, tok in enumerate(argv[:-1]):
@@ -871,6 +929,22 @@ def parse_args(argv):
         p.error("--overlap / --batch-size need --texture")
     if a.erode is not None and a.erode < 1:
         p.error("--erode must be >= 1")
+    if a.mesh is None:
+        if a.max_error is not None or a.tile is not None:
+            p.error("--max-error / --tile need --mesh")
+    else:
+        from . import mesh as _mesh
+        a.max_error = 0.01 if a.max_error is None else a.max_error
+        a.tile = 256 if a.tile is None else a.tile
+        if os.path.splitext(a.mesh)[1].lower() not in (".glb", ".obj", ".npz"):
+            p.error("--mesh must be .glb, .obj or .npz")
+        try:
+            _mesh._tile_log2(a.tile)
+            _mesh._check_error(a.max_error)
+        except ValueError as e:
+            p.error(str(e))
+        if any(v % a.tile for v in a.region):
+            p.error("--mesh needs a --region made of whole tiles: multiples of %d, got %s" % (a.tile, (a.region,)))
     return a
 
 
@@ -894,6 +968,10 @@ def main(argv=None):
             hm, tex = world._request(y0, x0, h, w, True, True, hm, tex, False, True)      # both(), fp32 + uint8
         else:
             hm = world.heightmap(y0, x0, h, w, out=hm)
+        if a.mesh:
+            m = world.mesh(y0, x0, h, w, a.max_error, tile=a.tile, texture=bool(a.texture))
+            m, mtex = m if a.texture else (m, None)
+            m.save(a.mesh, texture=mtex)
     if a.output.endswith(".npy"):
         hm.flush()
     else:
