@@ -194,6 +194,12 @@ SIGNATURES = {
     "ghm_mesh_errors": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32],
     "ghm_mesh_count": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "ghm_mesh_extract": [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _p, _p, _i64, _i64],
+    "ghm_hydrology_fill": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i32)],
+    "ghm_hydrology_flats": [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p, C.POINTER(_i64)],
+    "ghm_hydrology_directions": [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32],
+    "ghm_hydrology_accumulate": [_p, _p, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, C.POINTER(_i32)],
+    "ghm_hydrology_paint": [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _i32, _f, _f, _f, _f, _f, C.c_uint32, _i32, _i32, _p,
+                            _i32],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -245,6 +251,7 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_erosion_tile": ([_i32], C.c_int32),
             "ghm_skylight_lds_bytes": ([_i32], C.c_int64),
             "ghm_mesh_workspace": ([_i32, _i32], C.c_int64),
+            "ghm_hydrology_workspace": ([_i32, _i32], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

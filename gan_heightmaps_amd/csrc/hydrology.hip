@@ -1,0 +1,544 @@
+// Where the water is on a heightfield (gan_heightmaps_amd/hydrology.py): the filled surface F, the distance D to
+// the draining rim of the flats the filling leaves, one of eight flow directions per cell, the drainage area A and the outlet
+// every cell drains to.  Neighbours k = 0 .. 7 are N NE E SE S SW W NW; the cells of the first and last row and column are
+// outlets.
+//
+// F and D are fixed points of relaxations:
+//   F[c] = h[c] at an outlet, max(h[c], min_k F[n_k]) elsewhere, from F = +inf;
+//   D[c] = 0 at a draining cell (an outlet, or a cell with a strictly lower neighbour in F),
+//          min(SENTINEL, 1 + min D[n] over the neighbours with F[n] == F[c]) elsewhere, from D = SENTINEL.
+// Why any schedule gives the same bits.  Both maps are monotone: lower inputs never give a higher output.  The start lies above
+// the fixed point, so by induction every value ever computed, from inputs of any age, is (a) at or above the fixed point and
+// (b) at or below the value the cell held before, because each input was itself at or below what it was when the cell was
+// last computed.  A cell is written by one owner only, and a 32-bit load sees a value that was once stored.  So a tile may read
+// its neighbours' cells of either generation, mid-launch: it can only be late, never wrong.  The values are drawn from a finite
+// set (the heights; the integers up to SENTINEL), so the descent ends, and it ends at a state in which one more pass over every
+// cell changes nothing.  That state is the fixed point, and there is only one: a second one G >= F would have a cell whose
+// neighbours all keep it above F along a path that ends at an outlet, where G = F = h (tests/hydrology_ref.py holds the
+// relaxation against a heap priority-flood and a queue BFS, which are not relaxations).  Only max, min and an integer + 1 are
+// involved, and h is read as h + 0 (no -0), so nothing rounds and the forms agree bit for bit.
+// Two forms:
+//   plain : one launch is one Jacobi sweep between two global planes (the output and a workspace plane, alternating);
+//   tiled : a 256-thread block stages a 32 x 32 tile and its one-cell apron in LDS, sweeps it in place until it stops changing
+//           -- at most HYD_INNER times, a compile-time cap: no flag can spin a block -- and writes back the cells that fell.
+// A block that changed a cell stores 1 to one device word (one plain vector store per block, no atomics: every writer writes
+// the same value).  The host issues launches in groups, reads the word once per group, stops at the first group that changed
+// nothing and refuses to go beyond H W sweeps.
+//
+// A is the size of every cell's upstream tree, by pointer doubling: S_0 = 1, P_0 = the receiver (-1 at an outlet);
+// S_{k+1}[c] = S_k[c] + sum of S_k[d] over P_k(d) = c, P_{k+1}(d) = P_k(P_k(d)); the sums are 32-bit integer atomicAdd, exact
+// in any order.  The outlet of a cell comes from the same rounds, B_{k+1}(d) = B_k(B_k(d)) with B_0 = the receiver or the cell
+// itself at an outlet.
+#include "common.h"
+
+// the slope's subtraction and product are rounded one by one, and so are the paint's (tests/hydrology_ref.py restates them)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int HYD_TILE = GHM_HYDROLOGY_TILE;
+constexpr int HYD_LDS = HYD_TILE + 2;                 // the tile and its apron
+constexpr int HYD_INNER = GHM_HYDROLOGY_INNER_SWEEPS;
+constexpr int HYD_SENTINEL = GHM_HYDROLOGY_SENTINEL;
+constexpr int HYD_GROUP_PLAIN = 8, HYD_GROUP_TILED = 4;
+constexpr int HYD_MAX_ROUNDS = 32;
+constexpr int64_t HYD_HEADER = 256;                   // bytes in front of the workspace planes: the device words
+
+__device__ __constant__ const int HYD_DY[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
+__device__ __constant__ const int HYD_DX[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+
+__device__ __forceinline__ bool hyd_outlet(int r, int c, int H, int W) { return r == 0 || c == 0 || r == H - 1 || c == W - 1; }
+
+// one store per block that changed anything; every thread of the block arrives here
+__device__ __forceinline__ void hyd_raise(int changed, int* word) {
+    const int any = __syncthreads_or(changed);
+    if (any && threadIdx.x == 0 && threadIdx.y == 0) *word = 1;
+}
+
+// ---- step 1: the filled surface ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hyd_fill_init_kernel(const float* __restrict__ h, int ph, float* __restrict__ F, int pf,
+                                                            int H, int W) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= H || c >= W) return;
+    F[(long)r * pf + c] = hyd_outlet(r, c, H, W) ? h[(long)r * ph + c] + 0.0f : __builtin_inff();
+}
+
+__global__ __launch_bounds__(256) void hyd_fill_plain_kernel(const float* __restrict__ h, int ph, const float* __restrict__ src,
+                                                             int ps, float* __restrict__ dst, int pd, int H, int W, int* word) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    int changed = 0;
+    if (r < H && c < W) {
+        const float old = src[(long)r * ps + c];
+        float nv = old;
+        if (!hyd_outlet(r, c, H, W)) {
+            float m = __builtin_inff();
+#pragma unroll
+            for (int k = 0; k < 8; ++k) m = fminf(m, src[(long)(r + HYD_DY[k]) * ps + (c + HYD_DX[k])]);
+            nv = fmaxf(h[(long)r * ph + c] + 0.0f, m);
+        }
+        dst[(long)r * pd + c] = nv;
+        changed = nv != old;
+    }
+    hyd_raise(changed, word);
+}
+
+// thread tid of a tile's block owns the cells (tid / 32 + 8 n, tid % 32) of the tile, n = 0 .. 3
+__global__ __launch_bounds__(256) void hyd_fill_tiled_kernel(const float* __restrict__ h, int ph, float* F, int pf, int H, int W,
+                                                             int* word) {
+    __shared__ float t[HYD_LDS][HYD_LDS];
+    const int tid = threadIdx.x, ty = blockIdx.y * HYD_TILE, tx = blockIdx.x * HYD_TILE;
+    for (int n = tid; n < HYD_LDS * HYD_LDS; n += 256) {
+        const int lr = n / HYD_LDS, lc = n - lr * HYD_LDS;
+        const int r = ty - 1 + lr, c = tx - 1 + lc;
+        t[lr][lc] = (r >= 0 && r < H && c >= 0 && c < W) ? F[(long)r * pf + c] : __builtin_inff();
+    }
+    const int lc = (tid & 31) + 1, c = tx + (tid & 31);
+    float hv[4], first[4];
+    bool live[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int r = ty + (tid >> 5) + 8 * n;
+        live[n] = r < H && c < W && !hyd_outlet(r, c, H, W);
+        hv[n] = live[n] ? h[(long)r * ph + c] + 0.0f : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < 4; ++n) first[n] = t[(tid >> 5) + 8 * n + 1][lc];
+    for (int s = 0; s < HYD_INNER; ++s) {
+        int ch = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            if (!live[n]) continue;
+            const int lr = (tid >> 5) + 8 * n + 1;
+            float m = __builtin_inff();
+#pragma unroll
+            for (int k = 0; k < 8; ++k) m = fminf(m, t[lr + HYD_DY[k]][lc + HYD_DX[k]]);
+            const float nv = fmaxf(hv[n], m);
+            if (nv != t[lr][lc]) {
+                t[lr][lc] = nv;
+                ch = 1;
+            }
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+    int changed = 0;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        if (!live[n]) continue;
+        const int lr = (tid >> 5) + 8 * n + 1;
+        const float v = t[lr][lc];
+        if (v != first[n]) {
+            F[(long)(ty + lr - 1) * pf + c] = v;
+            changed = 1;
+        }
+    }
+    hyd_raise(changed, word);
+}
+
+// ---- step 2: the distance to the rim of a flat ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hyd_flat_init_kernel(const float* __restrict__ F, int pf, int* __restrict__ D, int pd,
+                                                            int H, int W) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= H || c >= W) return;
+    bool drains = hyd_outlet(r, c, H, W);
+    if (!drains) {
+        const float f = F[(long)r * pf + c];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) drains = drains || F[(long)(r + HYD_DY[k]) * pf + (c + HYD_DX[k])] < f;
+    }
+    D[(long)r * pd + c] = drains ? 0 : HYD_SENTINEL;
+}
+
+__global__ __launch_bounds__(256) void hyd_flat_plain_kernel(const float* __restrict__ F, int pf, const int* __restrict__ src,
+                                                             int ps, int* __restrict__ dst, int pd, int H, int W, int* word) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    int changed = 0;
+    if (r < H && c < W) {
+        const int old = src[(long)r * ps + c];
+        int nv = old;
+        if (old != 0) {                                  // a draining cell is 0 from the start; every other cell is inside
+            const float f = F[(long)r * pf + c];
+            int m = HYD_SENTINEL - 1;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int y = r + HYD_DY[k], x = c + HYD_DX[k];
+                if (F[(long)y * pf + x] == f) m = min(m, src[(long)y * ps + x]);
+            }
+            nv = m + 1;
+        }
+        dst[(long)r * pd + c] = nv;
+        changed = nv != old;
+    }
+    hyd_raise(changed, word);
+}
+
+__global__ __launch_bounds__(256) void hyd_flat_tiled_kernel(const float* __restrict__ F, int pf, int* D, int pd, int H, int W,
+                                                             int* word) {
+    __shared__ int t[HYD_LDS][HYD_LDS];
+    __shared__ float tf[HYD_LDS][HYD_LDS];
+    const int tid = threadIdx.x, ty = blockIdx.y * HYD_TILE, tx = blockIdx.x * HYD_TILE;
+    for (int n = tid; n < HYD_LDS * HYD_LDS; n += 256) {
+        const int lr = n / HYD_LDS, lc = n - lr * HYD_LDS;
+        const int r = ty - 1 + lr, c = tx - 1 + lc;
+        const bool in = r >= 0 && r < H && c >= 0 && c < W;
+        t[lr][lc] = in ? D[(long)r * pd + c] : HYD_SENTINEL;
+        tf[lr][lc] = in ? F[(long)r * pf + c] : __builtin_nanf("");        // equal to nothing
+    }
+    __syncthreads();
+    const int lc = (tid & 31) + 1, c = tx + (tid & 31);
+    int first[4];
+    unsigned same[4];                                    // bit k: neighbour k has this cell's F
+    bool live[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int lr = (tid >> 5) + 8 * n + 1, r = ty + lr - 1;
+        first[n] = t[lr][lc];
+        live[n] = r < H && c < W && first[n] != 0;     // not draining, so not an outlet either
+        same[n] = 0;
+        const float f = tf[lr][lc];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) same[n] |= (tf[lr + HYD_DY[k]][lc + HYD_DX[k]] == f ? 1u : 0u) << k;
+    }
+    for (int s = 0; s < HYD_INNER; ++s) {
+        int ch = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            if (!live[n]) continue;
+            const int lr = (tid >> 5) + 8 * n + 1;
+            int m = HYD_SENTINEL - 1;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (same[n] >> k & 1u) m = min(m, t[lr + HYD_DY[k]][lc + HYD_DX[k]]);
+            if (m + 1 != t[lr][lc]) {
+                t[lr][lc] = m + 1;
+                ch = 1;
+            }
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+    int changed = 0;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        if (!live[n]) continue;
+        const int lr = (tid >> 5) + 8 * n + 1;
+        const int v = t[lr][lc];
+        if (v != first[n]) {
+            D[(long)(ty + lr - 1) * pd + c] = v;
+            changed = 1;
+        }
+    }
+    hyd_raise(changed, word);
+}
+
+// ---- step 3: directions -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hyd_direction_kernel(const float* __restrict__ F, int pf, const int* __restrict__ D, int pd,
+                                                            int H, int W, signed char* __restrict__ dir, int pdir) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= H || c >= W) return;
+    int best = -1;
+    if (!hyd_outlet(r, c, H, W)) {
+        const float f = F[(long)r * pf + c];
+        float fn[8], s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            fn[k] = F[(long)(r + HYD_DY[k]) * pf + (c + HYD_DX[k])];
+            if (fn[k] < f) {
+                const float d = f - fn[k];
+                const float sk = d * ((k & 1) ? 0.70710678f : 1.0f);
+                if (best < 0 || sk > s) {
+                    s = sk;
+                    best = k;
+                }
+            }
+        }
+        if (best < 0) {
+            const int want = D[(long)r * pd + c] - 1;
+#pragma unroll
+            for (int k = 7; k >= 0; --k)
+                if (fn[k] == f && D[(long)(r + HYD_DY[k]) * pd + (c + HYD_DX[k])] == want) best = k;
+        }
+    }
+    dir[(long)r * pdir + c] = (signed char)best;
+}
+
+// ---- steps 4 and 5: accumulation and basins by pointer doubling ------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hyd_acc_init_kernel(const signed char* __restrict__ dir, int pdir, int H, int W,
+                                                           unsigned* __restrict__ S, int* __restrict__ P, int* __restrict__ B,
+                                                           int* word) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    int alive = 0;
+    if (r < H && c < W) {
+        const int d = dir[(long)r * pdir + c];
+        const int idx = r * W + c;
+        int p = -1;
+        if (d >= 0 && d < 8) {                           // anything else, and a receiver outside the plane, ends the chain
+            const int y = r + HYD_DY[d], x = c + HYD_DX[d];
+            if (y >= 0 && y < H && x >= 0 && x < W) p = y * W + x;
+        }
+        S[idx] = 1u;
+        P[idx] = p;
+        B[idx] = p >= 0 ? p : idx;
+        alive = p >= 0;
+    }
+    hyd_raise(alive, word);
+}
+
+// S1 holds a copy of S0 when this starts
+__global__ __launch_bounds__(256) void hyd_acc_round_kernel(const unsigned* __restrict__ S0, unsigned* S1,
+                                                            const int* __restrict__ P0, int* __restrict__ P1,
+                                                            const int* __restrict__ B0, int* __restrict__ B1, int n, int* word) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    int alive = 0;
+    if (idx < n) {
+        const int p = P0[idx];
+        int pp = -1;
+        if (p >= 0) {
+            atomicAdd(&S1[p], S0[idx]);
+            pp = P0[p];
+        }
+        P1[idx] = pp;
+        B1[idx] = B0[B0[idx]];
+        alive = pp >= 0;
+    }
+    hyd_raise(alive, word);
+}
+
+__global__ __launch_bounds__(256) void hyd_acc_emit_kernel(const unsigned* __restrict__ S, const int* __restrict__ B, int H, int W,
+                                                           unsigned* __restrict__ A, int pa, int* __restrict__ basin, int pb) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= H || c >= W) return;
+    A[(long)r * pa + c] = S[r * W + c];
+    basin[(long)r * pb + c] = B[r * W + c];
+}
+
+// ---- the water on a texture -------------------------------------------------------------------------------------------------------
+struct PaintArgs {
+    const float* depth;
+    const unsigned* acc;
+    const float* tex;
+    void* out;
+    int H, W, pdepth, pacc, ptex, pout, channels, width, out_u8;
+    unsigned threshold;
+    float colour[3], opacity, min_depth;
+};
+
+__global__ __launch_bounds__(256) void hyd_paint_kernel(const PaintArgs k) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= k.H || c >= k.W) return;
+    bool wet = k.depth[(long)r * k.pdepth + c] > k.min_depth;
+    if (!wet) {
+        unsigned m = 0;
+        for (int dy = -k.width; dy <= k.width; ++dy) {
+            const int y = min(max(r + dy, 0), k.H - 1);
+            for (int dx = -k.width; dx <= k.width; ++dx) m = max(m, k.acc[(long)y * k.pacc + min(max(c + dx, 0), k.W - 1)]);
+        }
+        wet = m >= k.threshold;
+    }
+    for (int ch = 0; ch < k.channels; ++ch) {
+        const float t = k.tex[((long)ch * k.H + r) * k.ptex + c];
+        float v = t;
+        if (wet) {
+            const float d = k.colour[ch] - t;
+            const float p = k.opacity * d;
+            v = t + p;
+        }
+        const long at = ((long)ch * k.H + r) * k.pout + c;
+        if (k.out_u8)                                    // the uint8 map of ghm_world_crop: rint((double)v * 255), half to even
+            ((unsigned char*)k.out)[at] = (unsigned char)(int)rint((double)fminf(fmaxf(v, 0.0f), 1.0f) * 255.0);
+        else
+            ((float*)k.out)[at] = v;
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+#define HYD_PLANE_GRID(H, W) dim3(ceil_div((W), 64), ceil_div((H), 4)), dim3(64, 4), 0, ctx->stream
+#define HYD_TILE_GRID(H, W) dim3(ceil_div((W), HYD_TILE), ceil_div((H), HYD_TILE)), dim3(256), 0, ctx->stream
+
+int hyd_check_plane(const char* who, int H, int W, int pitch, const char* what) {
+    GHM_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < ((int64_t)1 << 31) && H <= 4 * 65535,
+              "%s: a plane of %d x %d is out of range (H W < 2^31, H <= 262140)", who, H, W);
+    GHM_CHECK(pitch >= W && (int64_t)H * pitch < ((int64_t)1 << 31), "%s: the pitch of %s, %d, is out of range for %d x %d", who,
+              what, pitch, H, W);
+    return 0;
+}
+
+int hyd_sync_ok(ghm_ctx* ctx, const char* who) {
+    GHM_CHECK(ctx != nullptr, "%s: null context", who);
+    GHM_CHECK(!ctx->rec && !ctx->capturing, "%s waits for the device: it cannot be recorded or captured", who);
+    return 0;
+}
+
+int hyd_read_word(ghm_ctx* ctx, const int* word, int* value) {
+    GHM_LAUNCH_CHECK();
+    GHM_HIP(hipMemcpyAsync(value, word, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GHM_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// groups of sweeps until one group changes nothing; sweep(i) issues sweep number i
+template <class Sweep>
+int hyd_relax(ghm_ctx* ctx, const char* who, int* word, int group, int64_t cap, Sweep sweep, int64_t* sweeps, int32_t* changed) {
+    int64_t done = 0;
+    int any = 0;
+    for (;;) {
+        GHM_CHECK(done < cap, "%s: no fixed point within the hard cap of %lld sweeps", who, (long long)cap);
+        GHM_HIP(hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+        const int64_t n = cap - done < group ? cap - done : group;
+        for (int64_t i = 0; i < n; ++i) sweep(done + i);
+        int w = 0;
+        if (int rc = hyd_read_word(ctx, word, &w)) return rc;
+        done += n;
+        if (!w) break;
+        any = 1;
+    }
+    if (sweeps) *sweeps = done;
+    if (changed) *changed = any;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ghm_hydrology_workspace(int32_t H, int32_t W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return -1;
+    return HYD_HEADER + 6 * (int64_t)sizeof(int32_t) * H * W;
+}
+
+int ghm_hydrology_fill(ghm_ctx* ctx, const float* h, int32_t H, int32_t W, int32_t pitch, int32_t tiled, int32_t resume,
+                       float* filled, int32_t f_pitch, void* workspace, int64_t* sweeps, int32_t* changed) {
+    if (int rc = hyd_sync_ok(ctx, "ghm_hydrology_fill")) return rc;
+    GHM_CHECK(h && filled && workspace, "ghm_hydrology_fill: null pointer");
+    if (int rc = hyd_check_plane("ghm_hydrology_fill", H, W, pitch, "h")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_fill", H, W, f_pitch, "filled")) return rc;
+    int* word = (int*)workspace;
+    float* other = (float*)((char*)workspace + HYD_HEADER);
+    if (!resume) hipLaunchKernelGGL(hyd_fill_init_kernel, HYD_PLANE_GRID(H, W), h, pitch, filled, f_pitch, H, W);
+    const int64_t cap = (int64_t)H * W;
+    if (tiled)
+        return hyd_relax(ctx, "ghm_hydrology_fill", word, HYD_GROUP_TILED, cap, [&](int64_t) {
+            hipLaunchKernelGGL(hyd_fill_tiled_kernel, HYD_TILE_GRID(H, W), h, pitch, filled, f_pitch, H, W, word);
+        }, sweeps, changed);
+    // the first group that changes nothing leaves the same plane on both sides, whatever the parity of the count
+    return hyd_relax(ctx, "ghm_hydrology_fill", word, HYD_GROUP_PLAIN, cap, [&](int64_t i) {
+        if (i & 1)
+            hipLaunchKernelGGL(hyd_fill_plain_kernel, HYD_PLANE_GRID(H, W), h, pitch, other, W, filled, f_pitch, H, W, word);
+        else
+            hipLaunchKernelGGL(hyd_fill_plain_kernel, HYD_PLANE_GRID(H, W), h, pitch, filled, f_pitch, other, W, H, W, word);
+    }, sweeps, changed);
+}
+
+int ghm_hydrology_flats(ghm_ctx* ctx, const float* filled, int32_t H, int32_t W, int32_t f_pitch, int32_t tiled, int32_t* flat,
+                        int32_t d_pitch, void* workspace, int64_t* sweeps) {
+    if (int rc = hyd_sync_ok(ctx, "ghm_hydrology_flats")) return rc;
+    GHM_CHECK(filled && flat && workspace, "ghm_hydrology_flats: null pointer");
+    if (int rc = hyd_check_plane("ghm_hydrology_flats", H, W, f_pitch, "filled")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_flats", H, W, d_pitch, "flat")) return rc;
+    int* word = (int*)workspace;
+    int* other = (int*)((char*)workspace + HYD_HEADER);
+    hipLaunchKernelGGL(hyd_flat_init_kernel, HYD_PLANE_GRID(H, W), filled, f_pitch, flat, d_pitch, H, W);
+    const int64_t cap = (int64_t)H * W;
+    if (tiled)
+        return hyd_relax(ctx, "ghm_hydrology_flats", word, HYD_GROUP_TILED, cap, [&](int64_t) {
+            hipLaunchKernelGGL(hyd_flat_tiled_kernel, HYD_TILE_GRID(H, W), filled, f_pitch, flat, d_pitch, H, W, word);
+        }, sweeps, nullptr);
+    return hyd_relax(ctx, "ghm_hydrology_flats", word, HYD_GROUP_PLAIN, cap, [&](int64_t i) {
+        if (i & 1)
+            hipLaunchKernelGGL(hyd_flat_plain_kernel, HYD_PLANE_GRID(H, W), filled, f_pitch, other, W, flat, d_pitch, H, W, word);
+        else
+            hipLaunchKernelGGL(hyd_flat_plain_kernel, HYD_PLANE_GRID(H, W), filled, f_pitch, flat, d_pitch, other, W, H, W, word);
+    }, sweeps, nullptr);
+}
+
+int ghm_hydrology_directions(ghm_ctx* ctx, const float* filled, int32_t f_pitch, const int32_t* flat, int32_t d_pitch, int32_t H,
+                             int32_t W, int8_t* direction, int32_t dir_pitch) {
+    GHM_CHECK(ctx && filled && flat && direction, "ghm_hydrology_directions: null pointer");
+    if (int rc = hyd_check_plane("ghm_hydrology_directions", H, W, f_pitch, "filled")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_directions", H, W, d_pitch, "flat")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_directions", H, W, dir_pitch, "direction")) return rc;
+    hipLaunchKernelGGL(hyd_direction_kernel, HYD_PLANE_GRID(H, W), filled, f_pitch, flat, d_pitch, H, W, (signed char*)direction,
+                       dir_pitch);
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+int ghm_hydrology_accumulate(ghm_ctx* ctx, const int8_t* direction, int32_t dir_pitch, int32_t H, int32_t W, uint32_t* accumulation,
+                             int32_t a_pitch, int32_t* basin, int32_t b_pitch, void* workspace, int32_t* rounds) {
+    if (int rc = hyd_sync_ok(ctx, "ghm_hydrology_accumulate")) return rc;
+    GHM_CHECK(direction && accumulation && basin && workspace, "ghm_hydrology_accumulate: null pointer");
+    if (int rc = hyd_check_plane("ghm_hydrology_accumulate", H, W, dir_pitch, "direction")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_accumulate", H, W, a_pitch, "accumulation")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_accumulate", H, W, b_pitch, "basin")) return rc;
+    const int n = H * W;
+    int* word = (int*)workspace;
+    char* base = (char*)workspace + HYD_HEADER;
+    const size_t bytes = sizeof(int32_t) * (size_t)n;
+    unsigned* S[2] = {(unsigned*)base, (unsigned*)(base + bytes)};
+    int* P[2] = {(int*)(base + 2 * bytes), (int*)(base + 3 * bytes)};
+    int* B[2] = {(int*)(base + 4 * bytes), (int*)(base + 5 * bytes)};
+    GHM_HIP(hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(hyd_acc_init_kernel, HYD_PLANE_GRID(H, W), (const signed char*)direction, dir_pitch, H, W, S[0], P[0], B[0],
+                       word);
+    int alive = 0, k = 0;
+    if (int rc = hyd_read_word(ctx, word, &alive)) return rc;
+    while (alive) {
+        // a forest needs at most ceil(log2(H W)) rounds; directions that hold a cycle never run out of live pointers
+        GHM_CHECK(k < HYD_MAX_ROUNDS, "ghm_hydrology_accumulate: pointers still alive after %d rounds: the directions are no forest",
+                  k);
+        const int a = k & 1, b = a ^ 1;
+        GHM_HIP(hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+        GHM_HIP(hipMemcpyAsync(S[b], S[a], bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(hyd_acc_round_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, S[a], S[b], P[a], P[b], B[a],
+                           B[b], n, word);
+        if (int rc = hyd_read_word(ctx, word, &alive)) return rc;
+        ++k;
+    }
+    hipLaunchKernelGGL(hyd_acc_emit_kernel, HYD_PLANE_GRID(H, W), S[k & 1], B[k & 1], H, W, accumulation, a_pitch, basin, b_pitch);
+    GHM_LAUNCH_CHECK();
+    if (rounds) *rounds = k;
+    return 0;
+}
+
+int ghm_hydrology_paint(ghm_ctx* ctx, const float* depth, int32_t depth_pitch, const uint32_t* accumulation, int32_t a_pitch,
+                        int32_t H, int32_t W, const float* texture, int32_t tex_pitch, int32_t channels, float colour0,
+                        float colour1, float colour2, float opacity, float lake_min_depth, uint32_t river_threshold,
+                        int32_t river_width, int32_t out_u8, void* out, int32_t out_pitch) {
+    GHM_CHECK(ctx && depth && accumulation && texture && out, "ghm_hydrology_paint: null pointer");
+    if (int rc = hyd_check_plane("ghm_hydrology_paint", H, W, depth_pitch, "depth")) return rc;
+    if (int rc = hyd_check_plane("ghm_hydrology_paint", H, W, a_pitch, "accumulation")) return rc;
+    GHM_CHECK(channels == 1 || channels == 3, "ghm_hydrology_paint: channels=%d (1 or 3)", channels);
+    GHM_CHECK(tex_pitch >= W && out_pitch >= W && (int64_t)channels * H * tex_pitch < ((int64_t)1 << 31) &&
+                  (int64_t)channels * H * out_pitch < ((int64_t)1 << 31),
+              "ghm_hydrology_paint: texture pitches %d, %d out of range for %d x %d x %d", tex_pitch, out_pitch, channels, H, W);
+    GHM_CHECK(river_width >= 0 && river_width <= GHM_HYDROLOGY_MAX_RIVER_WIDTH, "ghm_hydrology_paint: river_width=%d (0 .. %d)",
+              river_width, GHM_HYDROLOGY_MAX_RIVER_WIDTH);
+    GHM_CHECK(opacity >= 0.0f && opacity <= 1.0f, "ghm_hydrology_paint: opacity=%g outside [0, 1]", (double)opacity);
+    GHM_CHECK(lake_min_depth >= 0.0f && lake_min_depth <= 3.0e38f, "ghm_hydrology_paint: lake_min_depth=%g", (double)lake_min_depth);
+    GHM_CHECK(fabsf(colour0) <= 3.0e38f && fabsf(colour1) <= 3.0e38f && fabsf(colour2) <= 3.0e38f,
+              "ghm_hydrology_paint: the colour is not finite");
+    PaintArgs k;
+    k.depth = depth;
+    k.acc = accumulation;
+    k.tex = texture;
+    k.out = out;
+    k.H = H;
+    k.W = W;
+    k.pdepth = depth_pitch;
+    k.pacc = a_pitch;
+    k.ptex = tex_pitch;
+    k.pout = out_pitch;
+    k.channels = channels;
+    k.width = river_width;
+    k.out_u8 = out_u8 ? 1 : 0;
+    k.threshold = river_threshold;
+    k.colour[0] = colour0;
+    k.colour[1] = colour1;
+    k.colour[2] = colour2;
+    k.opacity = opacity;
+    k.min_depth = lake_min_depth;
+    hipLaunchKernelGGL(hyd_paint_kernel, HYD_PLANE_GRID(H, W), k);
+    GHM_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

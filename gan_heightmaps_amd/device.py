@@ -1208,6 +1208,50 @@ class Ops:
              int(tile_log2), int(y0), int(x0), int(h), int(w), float(max_error), _vp(workspace_ptr), _vp(index_ptr),
              _vp(grid_ptr), _vp(heights_ptr), _vp(triangles_ptr), int(vertices), int(triangles))
 
+    # hydrology (csrc/hydrology.hip, gan_heightmaps_amd/hydrology.py)
+    @staticmethod
+    def hydrology_workspace(H, W):
+        """bytes of device workspace the hydrology entry points need for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_hydrology_workspace(int(H), int(W)))
+
+    def hydrology_fill(self, h_ptr, H, W, pitch, tiled, filled_ptr, f_pitch, workspace_ptr, resume=False):
+        """the filled surface of the fp32 plane at h_ptr (H x W, rows of ``pitch`` cells) -> the fp32 plane at filled_ptr;
+        resume: filled_ptr already holds a surface at or above the answer.  Returns (sweeps, changed); waits for the stream"""
+        sweeps, changed = C.c_int64(0), C.c_int32(0)
+        call("ghm_hydrology_fill", self.h, _vp(h_ptr), int(H), int(W), int(pitch), int(bool(tiled)), int(bool(resume)),
+             _vp(filled_ptr), int(f_pitch), _vp(workspace_ptr), C.byref(sweeps), C.byref(changed))
+        return int(sweeps.value), bool(changed.value)
+
+    def hydrology_flats(self, filled_ptr, H, W, f_pitch, tiled, flat_ptr, d_pitch, workspace_ptr):
+        """the distance of every cell to the draining rim of its flat -> the int32 plane at flat_ptr.  Returns the sweeps;
+        waits for the stream"""
+        sweeps = C.c_int64(0)
+        call("ghm_hydrology_flats", self.h, _vp(filled_ptr), int(H), int(W), int(f_pitch), int(bool(tiled)), _vp(flat_ptr),
+             int(d_pitch), _vp(workspace_ptr), C.byref(sweeps))
+        return int(sweeps.value)
+
+    def hydrology_directions(self, filled_ptr, f_pitch, flat_ptr, d_pitch, H, W, dir_ptr, dir_pitch):
+        """one of the eight directions, or -1 at an outlet, per cell -> the int8 plane at dir_ptr; asynchronous"""
+        call("ghm_hydrology_directions", self.h, _vp(filled_ptr), int(f_pitch), _vp(flat_ptr), int(d_pitch), int(H), int(W),
+             _vp(dir_ptr), int(dir_pitch))
+
+    def hydrology_accumulate(self, dir_ptr, dir_pitch, H, W, acc_ptr, a_pitch, basin_ptr, b_pitch, workspace_ptr):
+        """the drainage area (uint32) and the outlet (int32, a flat index) of every cell.  Returns the doubling rounds;
+        waits for the stream"""
+        rounds = C.c_int32(0)
+        call("ghm_hydrology_accumulate", self.h, _vp(dir_ptr), int(dir_pitch), int(H), int(W), _vp(acc_ptr), int(a_pitch),
+             _vp(basin_ptr), int(b_pitch), _vp(workspace_ptr), C.byref(rounds))
+        return int(rounds.value)
+
+    def hydrology_paint(self, depth_ptr, depth_pitch, acc_ptr, a_pitch, H, W, tex_ptr, tex_pitch, channels, colour, opacity,
+                        lake_min_depth, river_threshold, river_width, out_u8, out_ptr, out_pitch):
+        """the water on a texture of ``channels`` fp32 planes -> out_ptr, fp32 or uint8; colour: three values in the
+        texture's range; asynchronous"""
+        call("ghm_hydrology_paint", self.h, _vp(depth_ptr), int(depth_pitch), _vp(acc_ptr), int(a_pitch), int(H), int(W),
+             _vp(tex_ptr), int(tex_pitch), int(channels), float(colour[0]), float(colour[1]), float(colour[2]),
+             float(opacity), float(lake_min_depth), int(river_threshold), int(river_width), int(bool(out_u8)), _vp(out_ptr),
+             int(out_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

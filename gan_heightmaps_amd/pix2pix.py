@@ -197,6 +197,33 @@ class Pix2Pix:
         self.engine.sync()
         return heightmap_mesh(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, max_error, tile=tile, fused=fused)
 
+    def heightmap_hydrology(self, heightmap, **kw):
+        """Where the water is on a heightmap: filled lakes, flow directions, drainage area and basins, computed on the GPU
+        (gan_heightmaps_amd/hydrology.py).  Not in the reference.  heightmap: (H, W) or (1, H, W), floating point
+        (what a greyscale generator returns) or uint8; the array's edge is the outlet.  kw: analyse's (tiled, keep).
+        Returns a hydrology.Hydrology with the planes ``filled``, ``depth``, ``direction``, ``accumulation`` and ``basin``.
+        Leaves the training state untouched."""
+        from .hydrology import analyse
+        from .step import LANE_OF
+        self.engine.sync()
+        return analyse(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, **kw)
+
+    def paint_water(self, texture, hydro, water=None):
+        """The lakes and rivers of ``hydro`` (heightmap_hydrology's) painted on a texture of the same size.  Not
+        in the reference.  texture: as this model's generators or the uint8 paths return it; water: a hydrology.Water
+        (default Water()).  Returns the painted texture in the form it came in; dry pixels are untouched.  Intended use:
+
+            hydro = model.heightmap_hydrology(heightmap)
+            painted = model.paint_water(texture, hydro)
+            Scene(hydro.filled, painted)                                            # renders lakes as flat blue surfaces
+            model.heightmap_mesh(hydro.filled, 0.01).save(path, texture=painted)    # exports them
+
+        Leaves the training state untouched."""
+        from .hydrology import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, hydro, water, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -726,6 +726,18 @@ class TerrainWorld:
             return m, self.texture(int(y0), int(x0), int(h) + 1, int(w) + 1, uint8=True)
         return m
 
+    def hydrology(self, y0, x0, h, w, **kw):
+        """the hydrology (hydrology.Hydrology) of ``self.heightmap(y0, x0, h, w)``, heights mapped as a scene's; a
+        plain or an eroded world.  kw: hydrology.analyse's (tiled, keep).
+        Drainage is a property of the rectangle, whose edge is the outlet: water that would flow on across the edge leaves
+        the map there, lakes cut by the edge are not filled, and areas count cells of the rectangle alone.  Unlike every
+        other query of the world, two rectangles do NOT agree where they overlap.  Nothing is cached and no seam is handled."""
+        from .hydrology import analyse
+        from .render import _unit_planes
+        hm = _unit_planes(self.heightmap(y0, x0, h, w), bool(self.model.is_a_grayscale), "heightmap")
+        hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
+        return analyse(self._ops, hm, **kw)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
