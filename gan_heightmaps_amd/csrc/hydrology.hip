@@ -30,6 +30,7 @@
 // in any order.  The outlet of a cell comes from the same rounds, B_{k+1}(d) = B_k(B_k(d)) with B_0 = the receiver or the cell
 // itself at an outlet.
 #include "common.h"
+#include "relax.h"      // hyd_raise, hyd_check_plane, hyd_sync_ok, hyd_read_word, hyd_relax: shared with route.hip
 
 // the slope's subtraction and product are rounded one by one, and so are the paint's (tests/hydrology_ref.py restates them)
 #pragma clang fp contract(off)
@@ -48,12 +49,6 @@ __device__ __constant__ const int HYD_DY[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
 __device__ __constant__ const int HYD_DX[8] = {0, 1, 1, 1, 0, -1, -1, -1};
 
 __device__ __forceinline__ bool hyd_outlet(int r, int c, int H, int W) { return r == 0 || c == 0 || r == H - 1 || c == W - 1; }
-
-// one store per block that changed anything; every thread of the block arrives here
-__device__ __forceinline__ void hyd_raise(int changed, int* word) {
-    const int any = __syncthreads_or(changed);
-    if (any && threadIdx.x == 0 && threadIdx.y == 0) *word = 1;
-}
 
 // ---- step 1: the filled surface ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hyd_fill_init_kernel(const float* __restrict__ h, int ph, float* __restrict__ F, int pf,
@@ -353,48 +348,6 @@ __global__ __launch_bounds__(256) void hyd_paint_kernel(const PaintArgs k) {
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 #define HYD_PLANE_GRID(H, W) dim3(ceil_div((W), 64), ceil_div((H), 4)), dim3(64, 4), 0, ctx->stream
 #define HYD_TILE_GRID(H, W) dim3(ceil_div((W), HYD_TILE), ceil_div((H), HYD_TILE)), dim3(256), 0, ctx->stream
-
-int hyd_check_plane(const char* who, int H, int W, int pitch, const char* what) {
-    GHM_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < ((int64_t)1 << 31) && H <= 4 * 65535,
-              "%s: a plane of %d x %d is out of range (H W < 2^31, H <= 262140)", who, H, W);
-    GHM_CHECK(pitch >= W && (int64_t)H * pitch < ((int64_t)1 << 31), "%s: the pitch of %s, %d, is out of range for %d x %d", who,
-              what, pitch, H, W);
-    return 0;
-}
-
-int hyd_sync_ok(ghm_ctx* ctx, const char* who) {
-    GHM_CHECK(ctx != nullptr, "%s: null context", who);
-    GHM_CHECK(!ctx->rec && !ctx->capturing, "%s waits for the device: it cannot be recorded or captured", who);
-    return 0;
-}
-
-int hyd_read_word(ghm_ctx* ctx, const int* word, int* value) {
-    GHM_LAUNCH_CHECK();
-    GHM_HIP(hipMemcpyAsync(value, word, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    GHM_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// groups of sweeps until one group changes nothing; sweep(i) issues sweep number i
-template <class Sweep>
-int hyd_relax(ghm_ctx* ctx, const char* who, int* word, int group, int64_t cap, Sweep sweep, int64_t* sweeps, int32_t* changed) {
-    int64_t done = 0;
-    int any = 0;
-    for (;;) {
-        GHM_CHECK(done < cap, "%s: no fixed point within the hard cap of %lld sweeps", who, (long long)cap);
-        GHM_HIP(hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
-        const int64_t n = cap - done < group ? cap - done : group;
-        for (int64_t i = 0; i < n; ++i) sweep(done + i);
-        int w = 0;
-        if (int rc = hyd_read_word(ctx, word, &w)) return rc;
-        done += n;
-        if (!w) break;
-        any = 1;
-    }
-    if (sweeps) *sweeps = done;
-    if (changed) *changed = any;
-    return 0;
-}
 
 }  // namespace
 

@@ -1252,6 +1252,40 @@ class Ops:
              float(opacity), float(lake_min_depth), int(river_threshold), int(river_width), int(bool(out_u8)), _vp(out_ptr),
              int(out_pitch))
 
+    # least-cost travel (csrc/route.hip, gan_heightmaps_amd/route.py)
+    @staticmethod
+    def route_workspace(H, W):
+        """bytes of device workspace the route entry points need for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_route_workspace(int(H), int(W)))
+
+    def route_weights(self, h_ptr, H, W, pitch, height_scale, grade, lake, ford, river_threshold, lake_min_depth, workspace_ptr,
+                      penalty_ptr=None, p_pitch=0, depth_ptr=None, depth_pitch=0, acc_ptr=None, a_pitch=0):
+        """the four edge planes of the fp32 plane at h_ptr (H x W, rows of ``pitch`` cells) -> the workspace; penalty (fp32),
+        depth (fp32) and accumulation (uint32) planes are optional, None means "not given"; asynchronous"""
+        call("ghm_route_weights", self.h, _vp(h_ptr), int(H), int(W), int(pitch), _vp(penalty_ptr), int(p_pitch), _vp(depth_ptr),
+             int(depth_pitch), _vp(acc_ptr), int(a_pitch), float(height_scale), float(grade), float(lake), float(ford),
+             int(river_threshold), float(lake_min_depth), _vp(workspace_ptr))
+
+    def route_relax(self, H, W, sources, tiled, cost_ptr, c_pitch, workspace_ptr, resume=False):
+        """the least cost from ``sources`` (flat indices i W + j) to every cell -> the uint32 plane at cost_ptr, over the edge
+        planes route_weights left in the workspace; resume: cost_ptr already holds a plane at or above the answer.  Returns
+        (sweeps, changed); waits for the stream"""
+        src = np.ascontiguousarray(sources, np.int64).reshape(-1)
+        if src.size and (src.min() < -(1 << 31) or src.max() >= 1 << 31):
+            raise ValueError("route_relax: a source index does not fit 32 bits")
+        src = src.astype(np.int32)
+        sweeps, changed = C.c_int64(0), C.c_int32(0)
+        call("ghm_route_relax", self.h, int(H), int(W), src.ctypes.data_as(C.POINTER(C.c_int32)) if src.size else None,
+             int(src.size), int(bool(tiled)), int(bool(resume)), _vp(cost_ptr), int(c_pitch), _vp(workspace_ptr),
+             C.byref(sweeps), C.byref(changed))
+        return int(sweeps.value), bool(changed.value)
+
+    def route_parents(self, cost_ptr, c_pitch, H, W, parent_ptr, p_pitch, workspace_ptr):
+        """the neighbour every cell leaves through -> the int8 plane at parent_ptr (-1 a source, -2 unreached), in the encoding
+        of hydrology_accumulate's directions; asynchronous"""
+        call("ghm_route_parents", self.h, _vp(cost_ptr), int(c_pitch), int(H), int(W), _vp(parent_ptr), int(p_pitch),
+             _vp(workspace_ptr))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

@@ -224,6 +224,33 @@ class Pix2Pix:
         self.engine.sync()
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, hydro, water, value_range=self.is_b_grayscale)
 
+    def heightmap_routes(self, heightmap, sources, **kw):
+        """How to get from anywhere on a heightmap to the nearest of ``sources`` ((row, col) cells: towns), and where the roads
+        would run: the least-cost travel field, computed on the GPU (gan_heightmaps_amd/route.py).  Not in the
+        reference.  heightmap: (H, W) or (1, H, W), floating point or uint8.  kw: route.field's (travel, hydro, penalty, tiled,
+        keep).  Returns a route.CostField with the planes ``cost``, ``parent``, ``territory`` and ``traffic`` and the methods
+        ``travel_cost(cell)`` and ``path(cell)``.  Intended use:
+
+            hydro = model.heightmap_hydrology(heightmap)
+            roads = model.heightmap_routes(hydro.filled, towns, hydro=hydro)      # lakes and rivers cost extra
+            painted = model.paint_roads(model.paint_water(texture, hydro), roads, roads.paths(villages))
+
+        Leaves the training state untouched."""
+        from .route import field
+        from .step import LANE_OF
+        self.engine.sync()
+        return field(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, sources, **kw)
+
+    def paint_roads(self, texture, cost_field, paths=(), road=None):
+        """Roads painted on a texture of the field's size (DESIGN §4u).  Not in the reference.  cost_field: heightmap_routes';
+        paths: what its ``path`` / ``paths`` return; with ``road.traffic_threshold`` the cells that at least so many cells travel
+        through are painted instead.  road: a route.Road (default Road()).  Returns the painted texture in the form it came in;
+        other pixels are untouched.  Leaves the training state untouched."""
+        from .route import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, cost_field, paths, road, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -33,6 +33,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
 
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
+        [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]]
 """
 import argparse
 import os
@@ -738,6 +739,25 @@ class TerrainWorld:
         hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
         return analyse(self._ops, hm, **kw)
 
+    def routes(self, y0, x0, h, w, sources, hydrology=False, **kw):
+        """the least-cost travel field (route.CostField) of ``self.heightmap(y0, x0, h, w)``, heights mapped as a
+        scene's; a plain or an eroded world.  sources: (row, col) cells in world coordinates inside the rectangle; the field's
+        ``origin`` is (y0, x0), so ``travel_cost`` and ``path`` take and return world coordinates too.  hydrology=True analyses
+        the rectangle first (``self.hydrology``) and routes on its filled surface, lakes and rivers costing travel.lake and
+        travel.ford.  kw: route.field's (travel, penalty, tiled, keep).
+        Routes are a property of the rectangle: ways that would leave it and come back are not seen, and with hydrology=True
+        the drainage is the rectangle's too.  Unlike every other query of the world, two rectangles do NOT agree where they
+        overlap.  Nothing is cached and no seam is handled."""
+        from .route import field
+        y0, x0 = int(y0), int(x0)
+        if hydrology:
+            hydro = self.hydrology(y0, x0, h, w, tiled=kw.get('tiled'))
+            return field(self._ops, hydro.filled, sources, hydro=hydro, origin=(y0, x0), **kw)
+        from .render import _unit_planes
+        hm = _unit_planes(self.heightmap(y0, x0, h, w), bool(self.model.is_a_grayscale), "heightmap")
+        hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
+        return field(self._ops, hm, sources, origin=(y0, x0), **kw)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -924,13 +944,30 @@ def parse_args(argv):
                    help="the mesh's tolerance in height units (heights are in [0, 1]; default 0.01)")
     p.add_argument("--tile", type=int, default=None, metavar="T",
                    help="the mesh's root square side, a power of two (default 256)")
-    # a region that starts with a negative number would read as an option: hand it over in the --region=... form
+    from .route import parse_cell
+    p.add_argument("--routes", default=None, metavar="OUT_PREFIX",
+                   help="also write the least-cost travel field of the region from the --from cells (world coordinates): "
+                        "OUT_PREFIX.cost.npy, .parent.npy, .territory.npy, .traffic.npy, and one OUT_PREFIX.path<i>.npy per --to")
+    p.add_argument("--from", dest="sources", type=parse_cell, action="append", metavar="Y,X", default=[],
+                   help="a source of --routes, inside the region; repeat for more")
+    p.add_argument("--to", dest="targets", type=parse_cell, action="append", metavar="Y,X", default=[],
+                   help="a cell whose path to its source --routes writes; repeat for more")
+    # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
-    for i, tok in enumerate(argv[:-1]):
-        if tok == "--region" and re.match(r"\s*-\d", argv[i + 1]):
-            argv[i:i + 2] = ["--region=" + argv[i + 1]]
-            break
+    for i in range(len(argv) - 2, -1, -1):
+        if argv[i] in ("--region", "--from", "--to") and re.match(r"\s*-\d", argv[i + 1]):
+            argv[i:i + 2] = [argv[i] + "=" + argv[i + 1]]
     a = p.parse_args(argv)
+    if a.routes is None:
+        if a.sources or a.targets:
+            p.error("--from / --to need --routes")
+    else:
+        if not a.sources:
+            p.error("--routes needs at least one --from Y,X")
+        y0, x0, h, w = a.region
+        for y, x in a.sources + a.targets:
+            if not (y0 <= y < y0 + h and x0 <= x < x0 + w):
+                p.error("the cell %d,%d lies outside the region %s" % (y, x, (a.region,)))
     if a.chunk_cells is not None and a.chunk_cells < 1:
         p.error("--chunk-cells must be >= 1")
     if not 1 <= a.batch_size <= MAX_BATCH:
@@ -984,6 +1021,12 @@ def main(argv=None):
             m = world.mesh(y0, x0, h, w, a.max_error, tile=a.tile, texture=bool(a.texture))
             m, mtex = m if a.texture else (m, None)
             m.save(a.mesh, texture=mtex)
+        if a.routes:
+            cf = world.routes(y0, x0, h, w, a.sources)
+            for k in ("cost", "parent", "territory", "traffic"):
+                np.save("%s.%s.npy" % (a.routes, k), getattr(cf, k))
+            for i, path in enumerate(cf.paths(a.targets)):
+                np.save("%s.path%d.npy" % (a.routes, i), path)
     if a.output.endswith(".npy"):
         hm.flush()
     else:
