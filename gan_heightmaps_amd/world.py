@@ -36,6 +36,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]]
 """
 import argparse
+import contextlib
 import os
 import re
 import sys
@@ -46,6 +47,7 @@ import numpy as np
 from . import erosion as _erosion
 from . import skylight as _skylight
 from . import layers as L
+from .chunk_cache import ChunkCache
 from .streaming import DownloadRing, check_uint8_channels, output_array, shift_accumulator, store_rows
 from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
 from . import terrain as _terrain
@@ -183,15 +185,33 @@ def plan_windows(footprints, snap, max_pixels):
 
 
 class _HostSinks:
-    """Where a request's finished rows go, the host form: one download ring per output (streaming.DownloadRing) into the
-    caller's arrays, both on one copy stream of their own so that finished rows go down while the next chunks run."""
+    """Where a request's finished rows go, and which it wants (``want_hm``, ``want_tex``), the host form: one download ring
+    per output (streaming.DownloadRing) into the caller's arrays -- ``out_hm`` and ``out_tex``, made here where the caller
+    gave none --, both on one copy stream of their own so that finished rows go down while the next chunks run."""
 
-    def __init__(self, world, rect, out_hm, out_tex, hm_u8, tex_u8):
-        self.world, self.rect = world, rect
+    def __init__(self, *, hm=False, tex=False, out_hm=None, out_tex=None, hm_u8=False, tex_u8=False):
+        self.want_hm, self.want_tex = hm, tex
         self.out_hm, self.out_tex, self.hm_u8, self.tex_u8 = out_hm, out_tex, hm_u8, tex_u8
-        self.cp = type(world._dev)(world._dev.index)
-        self.hm = self.tex = None
-        self.hdone = []
+        self.cp = self.hm = self.tex = None
+
+    outs = property(lambda self: (self.out_hm, self.out_tex))
+
+    def plan_hm(self):
+        C, (h, w) = self.world._geo.channels, self.rect[2:]
+        if self.hm_u8:
+            check_uint8_channels(C)
+        shape = ((h, w) if C == 1 else (h, w, 3)) if self.hm_u8 else (C, h, w)
+        self.out_hm = output_array(self.out_hm, shape, np.uint8 if self.hm_u8 else np.float32)
+
+    def plan_tex(self, c_out):
+        h, w = self.rect[2:]
+        if self.tex_u8:
+            check_uint8_channels(c_out)
+        self.out_tex = output_array(self.out_tex, (h, w, 3) if self.tex_u8 else (c_out, h, w),
+                                    np.uint8 if self.tex_u8 else np.float32)
+
+    def open(self):
+        self.cp = type(self.world._dev)(self.world._dev.index)
 
     def begin_hm(self):
         wd, (y0, x0, h, w), out = self.world, self.rect, self.out_hm
@@ -246,13 +266,15 @@ class _HostSinks:
 
 class _SceneSinks:
     """Where a request's finished rows go, the resident form: straight into the planes of a render scene on the
-    device -- hm fp32 [h, w] at hm_ptr, tex fp32 [3, h, w] at tex_ptr, mapped to [0, 1] by the sinks' kernels as render.Scene
-    maps them on the host.  No stage, no pinned buffer, no copy stream; a non-finite value sets the int32 at flag_ptr."""
+    device -- hm fp32 [h, w] at hm_ptr, tex fp32 [3, h, w] at tex_ptr (None: not wanted), mapped to [0, 1] by the sinks'
+    kernels as render.Scene maps them on the host.  No array to make, no stage, no pinned buffer, no copy stream; a
+    non-finite value sets the int32 at flag_ptr."""
 
-    def __init__(self, world, rect, hm_ptr, tex_ptr, flag_ptr):
-        self.world, self.rect = world, rect
+    def __init__(self, *, hm_ptr, tex_ptr, flag_ptr):
+        self.want_hm, self.want_tex = hm_ptr is not None, tex_ptr is not None
         self.hm_ptr, self.tex_ptr, self.flag_ptr = hm_ptr, tex_ptr, flag_ptr
-        self.hdone = []
+
+    plan_hm = plan_tex = open = tex_poll = finish = close = lambda self, *args: None
 
     def begin_hm(self):
         if self.world._geo.channels not in (1, 3):
@@ -279,14 +301,23 @@ class _SceneSinks:
         wd._uops.texture_finalize_scene(acc, self.Wp, wd._geo.out, self.c_out, r_lo, n, yr, ny, pad_y, nx, pad_x, wd.overlap,
                                         wd.model.is_b_grayscale, self.tex_ptr, h, w, self.flag_ptr)
 
-    def tex_poll(self):
-        pass
 
-    def finish(self):
-        pass
-
-    def close(self):
-        pass
+@contextlib.contextmanager
+def _flagged_planes(dev, sizes, sync):
+    """device planes of ``sizes`` bytes for requests through _SceneSinks and, last, their int32 flag, zeroed: one list, to
+    which the body may add.  What it holds when the body ends, or fails, is freed; sync: once the device is idle"""
+    bufs = []
+    try:
+        for n in sizes + (4,):
+            bufs.append(dev.alloc(n))
+        dev.memset_zero(bufs[-1], 4)
+        dev.sync()
+        yield bufs
+    finally:
+        if sync:
+            dev.sync()
+        for p in bufs:
+            dev.free(p)
 
 
 class TerrainWorld:
@@ -308,7 +339,7 @@ class TerrainWorld:
         if latent_fn is not None and not callable(latent_fn):
             raise ValueError("latent_fn must be callable as latent_fn(i, j)")
         self.model, self.seed, self.blend = model, int(seed), blend
-        self.batch_size, self.cache_mb, self.latent_fn = int(batch_size), cache_mb, latent_fn
+        self.batch_size, self.latent_fn = int(batch_size), latent_fn
         geo = TerrainGeometry(model.dcgan['gen'], 1, 1)          # refuses what split_generator refuses
         if 2 * geo.halo < geo.s:
             raise NotImplementedError("terrain_world: the trunk's halo (%d) is below half a cell (%d)" % (geo.halo, geo.s))
@@ -323,11 +354,10 @@ class TerrainWorld:
         self._K = self._c * geo.out
         self._win = self._c * geo.s + 2 * geo.halo
         self.overlap = check_overlap(geo.out, overlap)
-        self._chunk_bytes = geo.channels * self._K * self._K * 4
-        self._chunks = OrderedDict()                              # (a, b) -> device pointer, least recently used first
+        self._cache = ChunkCache(lambda n: self._dev.alloc(n), lambda p: self._dev.free(p),
+                                 geo.channels * self._K * self._K * 4, cache_mb)
         self._heads = OrderedDict()                               # (I, J) -> DevTensor [HEAD_BLOCK^2, nch s s]
-        self._pool, self._pinned, self._table = [], set(), None
-        self._version, self._closed = None, False
+        self._table, self._version, self._closed = None, None, False
         self.computed = 0                                         # raw chunks computed so far (a cache hit computes nothing)
         # ---- the eroded layer: _chunks holds eroded chunks, _raw what _compute makes; one LRU over both ----
         if erosion is not None:
@@ -344,7 +374,6 @@ class TerrainWorld:
                 raise ValueError("erosion: a window of %d x %d cells is beyond the kernels' range" % (n, n))
         self.erosion = erosion
         self.eroded = 0                                           # erosions run so far
-        self._raw, self._stamp, self._tick = OrderedDict(), {}, 0
         self._ero, self._fused = None, _erosion.DEFAULT_FUSED     # one window's states, allocated once; the kernels' form
         if verbose:
             print("terrain_world: seed %d, chunk_cells %d (%d px), blend %s, overlap %d%s"
@@ -354,6 +383,9 @@ class TerrainWorld:
     chunk_cells = property(lambda self: self._c)
     chunk_px = property(lambda self: self._K)
     geometry = property(lambda self: self._geo)
+    cache_mb = property(lambda self: self._cache.cache_mb)
+    _chunks = property(lambda self: self._cache.layers['e'])
+    _raw = property(lambda self: self._cache.layers['r'])
 
     def __enter__(self):
         return self
@@ -397,18 +429,10 @@ class TerrainWorld:
             self._version = eng.param_version
 
     def _drop(self):
-        for p in list(self._chunks.values()) + list(self._raw.values()):
-            self._pool.append(p)
-        self._chunks.clear()
-        self._raw.clear()
-        self._stamp.clear()
+        self._cache.drop()
         for t in self._heads.values():
             self._dev.free(t.ptr)
         self._heads.clear()
-        self._pinned = set()
-
-    def _capacity(self):
-        return int(self.cache_mb * (1 << 20)) // self._chunk_bytes
 
     def _head_block(self, I, J):
         if (I, J) in self._heads:
@@ -456,27 +480,10 @@ class TerrainWorld:
         self._ops.world_seed(table, i_lo, j_lo, ncy, ncx, geo.s, wy0, wx0, bil, self._tplan.input_nodes[0].out)
         for e in self._tprog:
             e[1]()
-        ptr = self._pool.pop() if self._pool else self._dev.alloc(self._chunk_bytes)
+        ptr = self._cache.buffer()
         self._ops.world_emit(self._tplan.out, geo.halo * geo.F, geo.halo * geo.F, self._K, ptr)
         self.computed += 1
         return ptr
-
-    # ---- the eroded layer ---------------------------------------------------------------------------------------------
-    def _touch(self, layer, key):
-        self._tick += 1
-        self._stamp[(layer, key)] = self._tick
-
-    def _evict_layers(self, keep, size):
-        """one LRU over raw ('r') and eroded ('e') chunks: the least recently used outside ``keep`` go until ``size`` fits"""
-        cap = self._capacity()
-        if size <= cap:
-            return
-        for _, (layer, k) in sorted((t, lk) for lk, t in self._stamp.items() if lk not in keep):
-            if size <= cap:
-                break
-            self._pool.append((self._chunks if layer == 'e' else self._raw).pop(k))
-            del self._stamp[(layer, k)]
-            size -= 1
 
     def _erode(self, srcs):
         """the window of one chunk: gathered from its resident raw chunks, eroded, its centre K x K -> a chunk buffer"""
@@ -495,75 +502,37 @@ class TerrainWorld:
             ops.world_crop(self._raw[key], 1, K, r0, c0, nr, nc, False, True, s1 + 4 * wy * n, n, wx)
         ops.erosion_init(s1, n, n, n, ero.height_scale, s0, n)
         fin = ops.erosion_iterate(self._ero_params, s0, s1, tmp, n, n, n, ero.iterations, self._fused)
-        ptr = self._pool.pop() if self._pool else dev.alloc(self._chunk_bytes)
+        ptr = self._cache.buffer()
         ops.erosion_emit(fin, n, n, n, ero.height_scale, E, E, K, K, False, ptr, K, K)
         self.eroded += 1
         return ptr
 
-    def _acquire_eroded(self, keys):
-        missing = [k for k in keys if k not in self._chunks]
-        if missing and self._udev is not self._dev:
-            self._dev.wait_for(self._udev)
-        keep = {('e', k) for k in set(keys) | self._pinned}
-        resident = lambda: len(self._chunks) + len(self._raw)
-        for k in keys:
-            if k in self._chunks:
-                self._touch('e', k)
-                continue
-            srcs = erosion_sources(k[0], k[1], self._K, self.erosion.halo)
-            need = keep | {('r', s[0]) for s in srcs}
-            for s in srcs:
-                if s[0] not in self._raw:
-                    self._evict_layers(need, resident() + 1)
-                    self._raw[s[0]] = self._compute(*s[0])
-                self._touch('r', s[0])
-            self._evict_layers(need, resident() + 1)
-            self._chunks[k] = self._erode(srcs)
-            self._touch('e', k)
-        self._pinned = set(keys)
-        self._evict_layers({('e', k) for k in keys}, resident())
-        self._trim_heads(4 * HEAD_BLOCK if self._capacity() else 0)
-        if missing and self._udev is not self._dev:
-            self._udev.wait_for(self._dev)
-
     def _acquire(self, keys):
-        """make the chunks ``keys`` resident (they stay so until the next _acquire), then evict down to the budget"""
-        if self.erosion is not None:
-            return self._acquire_eroded(keys)
-        missing = [k for k in keys if k not in self._chunks]
+        """make the chunks ``keys`` resident (they stay so until the next _acquire), then evict down to the budget.  A missing
+        chunk's sources (erosion_sources; none in a plain world) come first; they, these keys and the last call's are kept"""
+        cache, chunks = self._cache, self._chunks
+        missing = any(k not in chunks for k in keys)
         if missing and self._udev is not self._dev:
             self._dev.wait_for(self._udev)                        # a recycled buffer may still feed an earlier gather
+        keep = {('e', k) for k in set(keys) | cache.pinned}
         for k in keys:
-            if k in self._chunks:
-                self._chunks.move_to_end(k)
-            else:
-                # make room first: only what this call needs is held beyond the budget
-                self._evict(set(keys) | self._pinned, len(self._chunks) + 1)
-                self._chunks[k] = self._compute(*k)
-        self._pinned = set(keys)
-        self._evict(self._pinned, len(self._chunks))
-        self._trim_heads(4 * HEAD_BLOCK if self._capacity() else 0)
+            srcs = [] if self.erosion is None or k in chunks else erosion_sources(k[0], k[1], self._K, self.erosion.halo)
+            need = keep | {('r', s[0]) for s in srcs}
+            for s in srcs:
+                cache.get('r', s[0], need, lambda: self._compute(*s[0]))
+            cache.get('e', k, need, lambda: self._erode(srcs) if srcs else self._compute(*k))
+        cache.pinned = set(keys)
+        cache.evict({('e', k) for k in keys})
+        self._trim_heads(4 * HEAD_BLOCK if cache.capacity() else 0)
         if missing and self._udev is not self._dev:
             self._udev.wait_for(self._dev)
-
-    def _evict(self, keep, size):
-        if self.erosion is not None:
-            return self._evict_layers({('e', k) for k in keep}, size + len(self._raw))
-        cap = self._capacity()
-        for k in [k for k in self._chunks if k not in keep]:
-            if size <= cap:
-                break
-            self._pool.append(self._chunks.pop(k))
-            size -= 1
 
     def _release(self):
         """end of a request: nothing is pinned, the cache goes down to its budget, recycled buffers are freed"""
-        self._pinned = set()
-        self._evict(set(), len(self._chunks))
+        self._cache.pinned = set()
+        self._cache.evict(set())
         self._eng.sync()
-        for p in self._pool:
-            self._dev.free(p)
-        self._pool = []
+        self._cache.free_pool()
 
     def clear(self):
         """drop every cached chunk and head map (the next request computes what it needs)"""
@@ -579,9 +548,7 @@ class TerrainWorld:
             return
         self._eng.sync()
         self._drop()
-        for p in self._pool:
-            self._dev.free(p)
-        self._pool = []
+        self._cache.free_pool()
         if self._table is not None:
             self._dev.free(self._table.ptr)
             self._table = None
@@ -606,15 +573,16 @@ class TerrainWorld:
     def heightmap(self, y0, x0, h, w, out=None, uint8=False):
         """pixels [y0, y0 + h) x [x0, x0 + w) of the heightmap: (C_a, h, w) float32, or with uint8=True
         util.to_uint8(util.convert_to_rgb(.)) as (h, w) for a greyscale generator, (h, w, 3) otherwise"""
-        return self._request(y0, x0, h, w, True, False, out, None, uint8, False)[0]
+        return self._request((y0, x0, h, w), _HostSinks(hm=True, out_hm=out, hm_u8=uint8)).out_hm
 
     def texture(self, y0, x0, h, w, out=None, uint8=False):
         """the same pixels of the textured world: (C_out, h, w) float32, or with uint8=True the (h, w, 3) uint8 RGB"""
-        return self._request(y0, x0, h, w, False, True, None, out, False, uint8)[1]
+        return self._request((y0, x0, h, w), _HostSinks(tex=True, out_tex=out, tex_u8=uint8)).out_tex
 
     def both(self, y0, x0, h, w, out_heightmap=None, out_texture=None, uint8=False):
         """(heightmap, texture) of one rectangle from one pass over the chunks; bit for bit the two separate calls"""
-        return self._request(y0, x0, h, w, True, True, out_heightmap, out_texture, uint8, uint8)
+        return self._request((y0, x0, h, w), _HostSinks(hm=True, tex=True, out_hm=out_heightmap, out_tex=out_texture,
+                                                        hm_u8=uint8, tex_u8=uint8)).outs
 
     def scene(self, y0, x0, h, w, resident=False, sky=None, **kw):
         """the rectangle as a render.Scene with origin (y0, x0): ``both`` in float32, uploaded once.  Cameras are
@@ -640,6 +608,15 @@ class TerrainWorld:
         return Scene(hm, tex, origin=(y0, x0), value_range=(self.model.is_a_grayscale, self.model.is_b_grayscale),
                      device=self.model.device, sky=sky, margin=margin, **kw)
 
+    def _fill_planes(self, dev, requests, flag, what):
+        """requests [(rect, hm_ptr, tex_ptr)] into device planes (_flagged_planes), then one read of the flag they share"""
+        for rect, hm, tex in requests:
+            self._request(rect, _SceneSinks(hm_ptr=hm, tex_ptr=tex, flag_ptr=flag))
+        seen = np.zeros(1, np.int32)
+        dev.d2h(seen, flag, 4)
+        if seen[0]:
+            raise ValueError("%s non-finite values" % what)
+
     def _resident_scene(self, y0, x0, h, w, sky=None, **kw):
         from .render import Scene
         y0, x0, h, w = self._check_region(y0, x0, h, w)
@@ -649,14 +626,9 @@ class TerrainWorld:
             raise ValueError("this TerrainWorld is closed")
         dev = self.model.device
         margin = 0 if sky is None else sky.reach
-        bufs = []
-        try:
-            for n in (4 * h * w, 12 * h * w, 4):                  # the height plane, the three texture planes, the flag
-                bufs.append(dev.alloc(n))
+        with _flagged_planes(dev, (4 * h * w, 12 * h * w), sync=False) as bufs:    # the height plane, three texture planes
             hm, tex, flag = bufs
-            dev.memset_zero(flag, 4)
-            dev.sync()
-            grown = None
+            requests, grown = [((y0, x0, h, w), hm, tex)], None
             if sky is not None:
                 # the height plane of the grown rectangle: the same chunks, mapped as the scene's own plane is
                 gh, gw = h + 2 * margin, w + 2 * margin
@@ -664,18 +636,9 @@ class TerrainWorld:
                     raise ValueError("the scene grown by the sky's reach, %d x %d, is beyond 2^31 pixels" % (gh, gw))
                 grown = dev.alloc(4 * gh * gw)
                 bufs.append(grown)
-                self._request(y0 - margin, x0 - margin, gh, gw, True, False, None, None, False, False,
-                              scene=(grown, None, flag))
-            self._request(y0, x0, h, w, True, True, None, None, False, False, scene=(hm, tex, flag))
-            seen = np.zeros(1, np.int32)
-            dev.d2h(seen, flag, 4)
-            if seen[0]:
-                raise ValueError("the heightmap or the texture has non-finite values")
-        except Exception:
-            for p in bufs:
-                dev.free(p)
-            raise
-        dev.free(flag)
+                requests.insert(0, ((y0 - margin, x0 - margin, gh, gw), grown, None))
+            self._fill_planes(dev, requests, flag, "the heightmap or the texture has")
+            bufs[:] = [flag]                                      # the planes are the scene's from here
         return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), sky=sky, sky_src=grown, margin=margin, **kw)
 
     def mesh(self, y0, x0, h, w, max_error, tile=256, texture=False, fused=None):
@@ -703,29 +666,20 @@ class TerrainWorld:
             raise ValueError("the region grown by a ring of tiles, %d x %d, is at or beyond 2^31 vertices" % (gh, gw))
         gy, gx, gh, gw = self._check_region(y0 - tile, x0 - tile, gh, gw)
         self._bind()
-        dev = self._dev
-        bufs = []
-        try:
-            for n in (4 * gh * gw, 4):
-                bufs.append(dev.alloc(n))
-            grown, flag = bufs
-            dev.memset_zero(flag, 4)
-            dev.sync()
-            self._request(gy, gx, gh, gw, True, False, None, None, False, False, scene=(grown, None, flag))
-            seen = np.zeros(1, np.int32)
-            dev.d2h(seen, flag, 4)
-            if seen[0]:
-                raise ValueError("the heightmap has non-finite values")
+        with _flagged_planes(self._dev, (4 * gh * gw,), sync=True) as (grown, flag):
+            self._fill_planes(self._dev, [((gy, gx, gh, gw), grown, None)], flag, "the heightmap has")
             with _mesh.ErrorMap(self._ops, _mesh.DevicePlane(grown, gh, gw), tile=tile, fused=fused, origin=(gy, gx),
                                 own=False) as em:
                 m = em.extract(tol, rect=(tile, tile, int(h), int(w)))
-        finally:
-            dev.sync()
-            for p_ in bufs:
-                dev.free(p_)
         if texture:
             return m, self.texture(int(y0), int(x0), int(h) + 1, int(w) + 1, uint8=True)
         return m
+
+    def _unit_height(self, y0, x0, h, w):
+        """``self.heightmap(y0, x0, h, w)`` as one float32 plane in [0, 1], mapped as a scene's (the channels' mean)"""
+        from .render import _unit_planes
+        hm = _unit_planes(self.heightmap(y0, x0, h, w), bool(self.model.is_a_grayscale), "heightmap")
+        return hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
 
     def hydrology(self, y0, x0, h, w, **kw):
         """the hydrology (hydrology.Hydrology) of ``self.heightmap(y0, x0, h, w)``, heights mapped as a scene's; a
@@ -734,9 +688,7 @@ class TerrainWorld:
         the map there, lakes cut by the edge are not filled, and areas count cells of the rectangle alone.  Unlike every
         other query of the world, two rectangles do NOT agree where they overlap.  Nothing is cached and no seam is handled."""
         from .hydrology import analyse
-        from .render import _unit_planes
-        hm = _unit_planes(self.heightmap(y0, x0, h, w), bool(self.model.is_a_grayscale), "heightmap")
-        hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
+        hm = self._unit_height(y0, x0, h, w)                      # (the first request binds _ops)
         return analyse(self._ops, hm, **kw)
 
     def routes(self, y0, x0, h, w, sources, hydrology=False, **kw):
@@ -753,9 +705,7 @@ class TerrainWorld:
         if hydrology:
             hydro = self.hydrology(y0, x0, h, w, tiled=kw.get('tiled'))
             return field(self._ops, hydro.filled, sources, hydro=hydro, origin=(y0, x0), **kw)
-        from .render import _unit_planes
-        hm = _unit_planes(self.heightmap(y0, x0, h, w), bool(self.model.is_a_grayscale), "heightmap")
-        hm = hm[0] if hm.shape[0] == 1 else hm.astype(np.float64).mean(0).astype(np.float32)
+        hm = self._unit_height(y0, x0, h, w)
         return field(self._ops, hm, sources, origin=(y0, x0), **kw)
 
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
@@ -806,17 +756,16 @@ class TerrainWorld:
         with self.scene(*camera.footprint(max_dist), sky=sky, **skw) as scene:
             return scene.render(camera, max_dist=max_dist, **kw)
 
-    def _request(self, y0, x0, h, w, want_hm, want_tex, out_hm, out_tex, hm_u8, tex_u8, scene=None):
-        """the chunks, the tiles and the accumulator of one rectangle; finished rows leave through a sink: the host's arrays
-        (_HostSinks), or with scene=(hm_ptr, tex_ptr, flag_ptr) the device planes of a render scene (_SceneSinks)"""
-        y0, x0, h, w = self._check_region(y0, x0, h, w)
-        geo, K = self._geo, self._K
-        C = geo.channels
-        if want_hm and scene is None:
-            if hm_u8:
-                check_uint8_channels(C)
-            shape = ((h, w) if C == 1 else (h, w, 3)) if hm_u8 else (C, h, w)
-            out_hm = output_array(out_hm, shape, np.uint8 if hm_u8 else np.float32)
+    def _request(self, rect, sink):
+        """the chunks, the tiles and the accumulator of one rectangle; finished rows leave through ``sink`` (returned), which
+        says what is wanted: the host's arrays (_HostSinks), or the device planes of a render scene (_SceneSinks).  A sink
+        plans its outputs (plan_hm before anything touches a device), is opened once the engine is idle, and closed"""
+        y0, x0, h, w = rect = self._check_region(*rect)
+        sink.world, sink.rect, sink.hdone = self, rect, []
+        geo, K, C = self._geo, self._K, self._geo.channels
+        want_hm, want_tex = sink.want_hm, sink.want_tex
+        if want_hm:
+            sink.plan_hm()
         self._bind()
         eng, udev, uops = self._eng, self._udev, self._uops
         T, o, B = geo.out, self.overlap, self.batch_size
@@ -828,18 +777,12 @@ class TerrainWorld:
             if (inp.H, inp.W, u.H, u.W) != (T, T, T, T) or inp.Cc != C:
                 raise ValueError("the pix2pix generator takes %d x %d x %d tiles, the heightmap generator makes %d x %d x %d"
                                  % (inp.Cc, inp.H, inp.W, C, T, T))
-            if scene is None:
-                if tex_u8:
-                    check_uint8_channels(c_out)
-                out_tex = output_array(out_tex, (h, w, 3) if tex_u8 else (c_out, h, w), np.uint8 if tex_u8 else np.float32)
+            sink.plan_tex(c_out)
         a_lo, a_hi = axis_chunks(y0, h, K)
         b_lo, b_hi = axis_chunks(x0, w, K)
         eng.sync()
         acc = None
-        if scene is None:
-            sink = _HostSinks(self, (y0, x0, h, w), out_hm, out_tex, hm_u8, tex_u8)
-        else:
-            sink = _SceneSinks(self, (y0, x0, h, w), *scene)
+        sink.open()
         try:
             # ---- heightmap rows: one sink call per chunk row ----
             if want_hm:
@@ -903,7 +846,7 @@ class TerrainWorld:
             if acc is not None:
                 udev.free(acc)
             self._release()
-        return out_hm, out_tex
+        return sink
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------
@@ -1014,7 +957,7 @@ def main(argv=None):
         if a.texture:
             tex = np.lib.format.open_memmap(a.texture, mode="w+", dtype=np.uint8, shape=(h, w, 3)) \
                 if a.texture.endswith(".npy") else None
-            hm, tex = world._request(y0, x0, h, w, True, True, hm, tex, False, True)      # both(), fp32 + uint8
+            hm, tex = world._request(a.region, _HostSinks(hm=True, tex=True, out_hm=hm, out_tex=tex, tex_u8=True)).outs
         else:
             hm = world.heightmap(y0, x0, h, w, out=hm)
         if a.mesh:

@@ -382,6 +382,7 @@ def host_device_class():
 # ---- events, making and closing page-locked buffers, frees (all behind a sync) -- is counted in ``tally``, not ordered.
 def trace_device_class():
     import bisect
+    import ctypes
     from collections import Counter
 
     class Shared:
@@ -407,6 +408,8 @@ def trace_device_class():
             return ptr(int(v)) if v >= ARENA else int(v)
         if isinstance(v, (list, tuple)):
             return [norm(x) for x in v]
+        if isinstance(v, ctypes.Structure):                       # a parameter block: its type and its fields' values
+            return [type(v).__name__] + [norm(getattr(v, k)) for k, _ in v._fields_]
         return v if v is None or isinstance(v, str) else repr(v)
 
     class Event:

@@ -108,15 +108,16 @@ class _Counting(WD.TerrainWorld):
     def _compute(self, a, b):
         self.computed += 1
         self.log.append(('r', (a, b)))
-        return self._pool.pop() if self._pool else self._dev.alloc(self._chunk_bytes)
+        return self._cache.buffer()
 
     def _erode(self, srcs):
         assert all(s[0] in self._raw for s in srcs)               # every source is resident when its window is gathered
         self.eroded += 1
         self.log.append(('e', srcs[4][0]))
-        return self._pool.pop() if self._pool else self._dev.alloc(self._chunk_bytes)
+        return self._cache.buffer()
 
     def resident(self):
+        assert len(self._cache.order) == len(self._chunks) + len(self._raw)
         return len(self._chunks) + len(self._raw)
 
 
@@ -133,14 +134,14 @@ def test_one_lru_bounds_raw_and_eroded_chunks_together():
     assert (w.eroded, w.computed) == (3, 15)                                   # one more raw column
     # a budget of 11 chunks of 16 KB: a window's nine raw chunks and the pinned eroded ones never leave mid-step
     w = _Counting(erosion=ero, cache_mb=11 * 16 / 1024)
-    assert w._capacity() == 11
+    assert w._cache.capacity() == 11
     w._acquire(keys)
     assert (w.eroded, w.computed) == (2, 12) and w.resident() <= 11 and set(w._chunks) == set(keys)
-    assert ('r', (-1, -1)) not in w._stamp and ('r', (1, 2)) in w._stamp       # the least recently used went first
+    assert ('r', (-1, -1)) not in w._cache.order and ('r', (1, 2)) in w._cache.order       # the least recently used went first
     w._acquire([(5, 5)])
     assert set(w._chunks) >= {(5, 5)} and w.resident() <= 11
-    w._pinned = set()
-    w._evict(set(), len(w._chunks))
+    w._cache.pinned = set()
+    w._cache.evict(set())
     assert w.resident() <= 11
     # no budget at all: everything outside the step goes, a repeat recomputes
     w = _Counting(erosion=ero, cache_mb=0)
@@ -149,11 +150,48 @@ def test_one_lru_bounds_raw_and_eroded_chunks_together():
     w._acquire([(0, 1)])
     assert (w.eroded, w.computed) == (2, 18) and set(w._chunks) == {(0, 1)} and not w._raw
     w._drop()
-    assert not w._chunks and not w._raw and not w._stamp
+    assert not w._chunks and not w._raw and not w._cache.order
     # without erosion the raw layer does not exist
     w = _Counting()
     w._acquire(keys)
-    assert (w.eroded, w.computed) == (0, 2) and not w._raw and not w._stamp and set(w._chunks) == set(keys)
+    assert (w.eroded, w.computed) == (0, 2) and not w._raw and set(w._chunks) == set(keys)
+    assert set(w._cache.order) == {('e', k) for k in keys}                    # the one LRU order holds no raw entry either
+
+
+BUDGETS = (0, 1, 2, 3, 5, 8, 11, 20, 64)                          # chunks
+
+
+def test_the_cache_follows_the_model_of_its_policy():
+    """324 random request sequences (36 per budget), each on a plain and on an eroded world, against tests/world_cache_ref.py:
+    after every call the same chunks were made in the same order, the same keys are resident in each layer, and no buffer
+    is in two places (the layers and the recycling pool)"""
+    from tests.world_cache_ref import CacheModel
+    rng = np.random.RandomState(20)
+    worlds = {(n, eroded): _Counting(cache_mb=n * 16 / 1024, **({"erosion": ER.Erosion(iterations=3)} if eroded else {}))
+              for n in BUDGETS for eroded in (False, True)}
+    evictions = 0
+    for i in range(36 * len(BUDGETS)):
+        n = BUDGETS[i % len(BUDGETS)]
+        calls = []
+        for _ in range(rng.randint(1, 13)):
+            a, b, na, nb = rng.randint(-3, 6), rng.randint(-3, 4), rng.randint(1, 3), rng.randint(1, 5)
+            calls.append([(a + i_, b + j) for i_ in range(na) for j in range(nb)])      # 1..2 x 1..4 keys in [-3, 6]^2
+        for eroded in (False, True):
+            w, model = worlds[(n, eroded)], CacheModel(n, eroded)
+            assert w._cache.capacity() == n
+            w._drop()                                             # an empty cache; what it held waits in the pool
+            w.log = []
+            for keys in calls:
+                w._acquire(keys)
+                model.acquire(keys)
+                # (a plain world's chunks are what _compute makes, which _Counting logs as 'r')
+                assert w.log == [(l if eroded else 'r', k) for l, k in model.made], (i, eroded, keys)
+                assert set(w._chunks) == model.resident('e') and set(w._raw) == model.resident('r'), (i, eroded, keys)
+                assert list(w._cache.order) == model.lru and w._cache.pinned == set(keys)
+                ptrs = list(w._chunks.values()) + list(w._raw.values()) + w._cache.pool
+                assert len(ptrs) == len(set(ptrs)), (i, eroded, keys)
+            evictions += len(w.log) - len(set(w.log))
+    assert evictions > 1000                                       # chunks were made again after they had been evicted
 
 
 # ---- command lines --------------------------------------------------------------------------------------------------------

@@ -229,7 +229,7 @@ def test_eroded_requests_are_independent_bit_for_bit(small_model):
         ch, ct = cold.both(y0, x0, h, w)
         assert np.array_equal(ch, hm) and np.array_equal(ct, tex)
         assert np.array_equal(cold.texture(y0, x0, h, w), tex)
-        assert not cold._chunks and not cold._raw and not cold._heads and not cold._stamp
+        assert not cold._chunks and not cold._raw and not cold._heads and not cold._cache.order
     with m.terrain_world(42, chunk_cells=2, erosion=ERO, cache_mb=0.2) as tiny:        # twelve chunks of 16 KB: evictions
         assert np.array_equal(tiny.heightmap(*REQ), a) and len(tiny._chunks) + len(tiny._raw) <= 12
         assert np.array_equal(tiny.heightmap(-10, 60, 100, 120), b)
@@ -248,7 +248,8 @@ def test_eroded_counters_for_a_request_that_touches_four_chunks(small_model):
         assert (world.eroded, world.computed) == (4, 16)
     with small_model.terrain_world(7, chunk_cells=2) as raw:
         raw.heightmap(60, -68, 8, 8)
-        assert (raw.eroded, raw.computed) == (0, 4) and not raw._raw and not raw._stamp
+        assert (raw.eroded, raw.computed) == (0, 4) and not raw._raw
+        assert set(raw._cache.order) == {('e', k) for k in raw._chunks}        # nor a raw entry in the one LRU order
 
 
 def test_eroded_resident_scene_equals_the_host_scene(small_model):

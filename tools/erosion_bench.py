@@ -114,8 +114,8 @@ def world(size, iterations, dtype):
                 # the per-chunk split, from a warm cache of raw chunks: one trunk pass, one window's erosion
                 srcs = erosion_sources(0, 0, K, ero.halo)
                 w._acquire([(0, 0)])
-                trunk = sorted(timed(dev, lambda: w._pool.append(w._compute(40, 40)))[1] for _ in range(5))
-                erode = sorted(timed(dev, lambda: w._pool.append(w._erode(srcs)))[1] for _ in range(5))
+                trunk = sorted(timed(dev, lambda: w._cache.pool.append(w._compute(40, 40)))[1] for _ in range(5))
+                erode = sorted(timed(dev, lambda: w._cache.pool.append(w._erode(srcs)))[1] for _ in range(5))
                 res["per_chunk"] = {"chunk_px": K, "window_px": K + 2 * ero.halo,
                                     "trunk_ms": {"median": round(trunk[2], 3), "min": round(trunk[0], 3), "max": round(trunk[4], 3)},
                                     "erosion_ms": {"median": round(erode[2], 3), "min": round(erode[0], 3), "max": round(erode[4], 3)},
