@@ -156,6 +156,7 @@ SIGNATURES = {
     "ghm_upconv_collapse_batched": [_p, _p, _i32, _i32],
     "ghm_upconv_expand_batched": [_p, _p, _i32, _i32, _i32],
     "ghm_blconv_frame_sizes": [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)],
+    "ghm_blconv_frame_splits": [_p, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)],
     "ghm_blconv_frame_fwd": [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_blconv_frame_gather": [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p],
     "ghm_blconv_frame_dgrad": [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32],

@@ -380,6 +380,36 @@ static int bl_splits(long contraction, long tiles, int num_cu) {
     return s < 1 ? 1 : s;
 }
 
+// the split counts of the three frame products: one function each, shared by the entry point that launches and by
+// ghm_blconv_frame_splits
+static int bl_splits_fwd(int N, int C, int K, int n1, int n2, int num_cu) {
+    const int used = (2 * (n1 > n2 ? n1 : n2) + 31) / 32;                    // position tiles that hold output pixels
+    return bl_splits(3L * C, (long)(K / 32) * used * 6 * N, num_cu);
+}
+
+static int bl_splits_dgrad(int N, int C, int K, int n1, int n2, int num_cu) {
+    const int used = (2 * (n1 > n2 ? n1 : n2) + 2 + 31) / 32;                // array indices 0 .. 2 n + 1
+    return bl_splits(6L * K, (long)(C / 32) * used * 4 * N, num_cu);
+}
+
+static int bl_splits_wgrad(int N, int C, int K, int n1, int n2, int num_cu) {
+    const int npmin = n1 < n2 ? n1 : n2;                    // position pairs per (part, n): every split must own some of them
+    int splits = bl_splits((long)2 * N * (n1 + n2), (long)(K / 32) * (C / 32) * 9, num_cu);
+    if (splits > npmin / 4) splits = npmin / 4 > 0 ? npmin / 4 : 1;
+    return splits;
+}
+
+// out[3] <- the split counts ghm_blconv_frame_fwd / _dgrad / _wgrad launch with on ``ctx`` (null: the CU count of
+// ghm_plan_cus).  Host only.
+int ghm_blconv_frame_splits(ghm_ctx* ctx, int32_t N, int32_t C, int32_t K, int32_t n1, int32_t n2, int32_t* out) {
+    GHM_CHECK(bl_ok(N, C, K, n1, n2), "ghm_blconv_frame_splits: geometry not served");
+    const int cus = ctx ? ctx->num_cu : ghm_plan_cus();
+    out[0] = bl_splits_fwd(N, C, K, n1, n2, cus);
+    out[1] = bl_splits_dgrad(N, C, K, n1, n2, cus);
+    out[2] = bl_splits_wgrad(N, C, K, n1, n2, cus);
+    return 0;
+}
+
 // y_pp [N, 4K, n1, n2] (parity-planar output of the collapsed convolution, sample stride ``ys``) += conv3x3(frame of x);
 // x: the coarse fp32 input [N, C, n1, n2]; wp: the FINE packed 3x3 weights [C][9][K]; FL: ghm_blconv_frame_sizes floats, kept
 // for the backward pass
@@ -391,7 +421,7 @@ int ghm_blconv_frame_fwd(ghm_ctx* ctx, const float* x, int64_t x_nstride, const 
                        FL + ((long)N * 4 * C * g.LP + 64));
     GHM_LAUNCH_CHECK();
     const int used = (2 * (n1 > n2 ? n1 : n2) + 31) / 32;                    // position tiles that hold output pixels
-    const int splits = bl_splits(3L * C, (long)(K / 32) * used * 6 * N, ctx->num_cu);
+    const int splits = bl_splits_fwd(N, C, K, n1, n2, ctx->num_cu);
     void* ws;
     if (ghm_scratch(ctx, (size_t)splits * 6 * N * K * g.LP * 4, &ws)) return -1;
     hipLaunchKernelGGL(bl_gemm_fwd_kernel, dim3(K / 32, used, splits * 6 * N), dim3(256), 0, ctx->stream, wp, (const float*)FL, g, splits,
@@ -421,7 +451,7 @@ int ghm_blconv_frame_dgrad(ghm_ctx* ctx, const float* DYL, const float* wp, floa
     GHM_CHECK(bl_ok(N, C, K, n1, n2), "ghm_blconv_frame_dgrad: geometry not served");
     const BlGeo g{N, C, K, n1, n2, bl_lp(n1, n2)};
     const int used = (2 * (n1 > n2 ? n1 : n2) + 2 + 31) / 32;                // array indices 0 .. 2 n + 1
-    const int splits = bl_splits(6L * K, (long)(C / 32) * used * 4 * N, ctx->num_cu);
+    const int splits = bl_splits_dgrad(N, C, K, n1, n2, ctx->num_cu);
     void* ws;
     const size_t part_bytes = (size_t)splits * N * 4 * C * g.LP * 4;
     if (ghm_scratch(ctx, part_bytes + (size_t)9 * K * C * 4, &ws)) return -1;
@@ -447,9 +477,7 @@ int ghm_blconv_frame_wgrad(ghm_ctx* ctx, const float* DYL, const float* FL, floa
                            int32_t n2) {
     GHM_CHECK(bl_ok(N, C, K, n1, n2), "ghm_blconv_frame_wgrad: geometry not served");
     const BlGeo g{N, C, K, n1, n2, bl_lp(n1, n2)};
-    const int npmin = n1 < n2 ? n1 : n2;                    // position pairs per (part, n): every split must own some of them
-    int splits = bl_splits((long)2 * N * (n1 + n2), (long)(K / 32) * (C / 32) * 9, ctx->num_cu);
-    if (splits > npmin / 4) splits = npmin / 4 > 0 ? npmin / 4 : 1;
+    const int splits = bl_splits_wgrad(N, C, K, n1, n2, ctx->num_cu);
     if (splits == 1) {          // enough tiles to fill the chip: one launch, the tiles added straight into dwp
         hipLaunchKernelGGL(bl_gemm_wgrad_kernel, dim3(K / 32, C / 32, 9), dim3(256), 0, ctx->stream,
                            DYL + (long)6 * N * K * (g.LP + 32), FL + ((long)N * 4 * C * g.LP + 64), g, 1, (float*)nullptr, dwp);

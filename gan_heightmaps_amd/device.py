@@ -504,6 +504,12 @@ class Ops:
         call("ghm_blconv_frame_sizes", int(N), int(Cc), int(K), int(n1), int(n2), C.byref(a), C.byref(b))
         return a.value, b.value
 
+    def blconv_frame_splits(self, N, Cc, K, n1, n2):
+        """(forward, data-gradient, weight-gradient) split-K counts the frame products launch with on this device"""
+        out = (C.c_int32 * 3)()
+        call("ghm_blconv_frame_splits", self.h, int(N), int(Cc), int(K), int(n1), int(n2), out)
+        return tuple(out)
+
     def blconv_frame_fwd(self, x, wp, y_pp, K, FL):
         """y_pp [N, 4K, n1, n2] += conv3x3(frame of x); x: the coarse fp32 input; wp: the layer's packed 3x3 weights"""
         call("ghm_blconv_frame_fwd", self.h, _vp(x), x.nstride, _vp(wp), _vp(y_pp), y_pp.nstride, x.N, x.Cc, int(K), x.H, x.W, _vp(FL))

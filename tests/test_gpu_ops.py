@@ -699,7 +699,7 @@ def test_upscale_conv5_collapsed_to_four_3x3(gpu, case):
 
 
 @pytest.mark.parametrize("case", [(2, 32, 32, 5, 7), (1, 32, 64, 2, 2), (2, 64, 32, 8, 16), (1, 96, 32, 16, 16), (3, 32, 32, 2, 9),
-                                  (4, 64, 64, 32, 32)])
+                                  (4, 64, 64, 32, 32), (1, 256, 128, 2, 3), (4, 1024, 512, 4, 4)])
 def test_bilinear_conv3_collapsed_onto_the_coarse_grid(gpu, case):
     """BilinearUpsample2DLayer(2) -> Conv2DLayer(3x3, 'same') (p2p.py:204-267, layers.py:13-26) without the up-sampled tensor:
     the collapsed 3x3 convolution with 4K filters on the coarse input (ghm_upconv_collapse_batched mode 1) + the frame the
