@@ -33,7 +33,8 @@ import sys
 
 import numpy as np
 
-from .util import is_int as _is_int, read_image
+from .planes import as_plane, check_size, scratch
+from .util import form_choice, is_int as _is_int, is_number as _is_number, read_image
 
 __all__ = ["RADIUS", "PLANES", "PARAMS", "DEFAULT_FUSED", "Erosion", "erode", "workspace_planes", "parse_args", "main"]
 
@@ -72,8 +73,7 @@ class Erosion:
         object.__setattr__(self, "iterations", int(self.iterations))
         for k in PARAMS:
             v = getattr(self, k)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
-                    or v < 0 or np.float32(v) > np.float32(3e38):
+            if not _is_number(v) or v < 0 or np.float32(v) > np.float32(3e38):
                 raise ValueError("%s must be a finite number >= 0, got %r" % (k, v))
             object.__setattr__(self, k, float(v))
         if not self.dt > 0:
@@ -106,26 +106,9 @@ def workspace_planes(fused):
     return 2 * PLANES + (0 if fused else 3)
 
 
-def _as_plane(heightmap):
+def _plane(heightmap):
     """-> (float32 [H, W] in [0, 1], whether the input had a leading channel axis)"""
-    a = heightmap if hasattr(heightmap, "dtype") else np.asarray(heightmap)
-    lead = a.ndim == 3
-    if lead:
-        if a.shape[0] != 1:
-            raise ValueError("erosion needs one height per pixel: a (H, W) or (1, H, W) heightmap, got %s"
-                             % (tuple(a.shape),))
-        a = a[0]
-    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("heightmap must be (H, W) or (1, H, W), got %s" % (tuple(np.shape(heightmap)),))
-    if a.dtype == np.uint8:
-        a = np.asarray(a).astype(np.float32) / np.float32(255)
-    elif a.dtype.kind == "f":
-        a = np.ascontiguousarray(a, np.float32)
-    else:
-        raise ValueError("heightmap must be uint8 or floating point in [0, 1], got %s" % a.dtype)
-    if not np.isfinite(a).all():
-        raise ValueError("the heightmap has non-finite values")
-    return np.ascontiguousarray(a), lead
+    return as_plane(heightmap, what="erosion"), np.ndim(heightmap) == 3
 
 
 def erode(device_ops, heightmap, erosion=None, fused=None, water=False, out=None, uint8=False):
@@ -140,10 +123,9 @@ def erode(device_ops, heightmap, erosion=None, fused=None, water=False, out=None
     if not isinstance(erosion, Erosion):
         raise ValueError("erosion must be an Erosion, got %r" % (erosion,))
     fused = DEFAULT_FUSED if fused is None else bool(fused)
-    a, lead = _as_plane(heightmap)
+    a, lead = _plane(heightmap)
     H, W = a.shape
-    if H * W >= 1 << 31 or H > 4 * 65535:
-        raise ValueError("heightmap size %d x %d out of range" % (H, W))
+    check_size(H, W)
     shape = (1, H, W) if lead else (H, W)
     dtype = np.uint8 if uint8 else np.float32
     if out is None:
@@ -152,15 +134,12 @@ def erode(device_ops, heightmap, erosion=None, fused=None, water=False, out=None
         raise ValueError("out must be a contiguous %s %s, got %s %s" % (np.dtype(dtype), shape, out.dtype, tuple(out.shape)))
     ops, dev = device_ops, device_ops.dev
     plane = 4 * H * W
-    bufs = []
-    try:
-        for n in (plane, PLANES * plane, PLANES * plane) + (() if fused else (3 * plane,)):
-            bufs.append(dev.alloc(n))
-        hm, s0, s1 = bufs[:3]
+    with scratch(dev) as alloc:
+        hm, s0, s1 = alloc(plane), alloc(PLANES * plane), alloc(PLANES * plane)
+        uvs = None if fused else alloc(3 * plane)
         dev.h2d(hm, a)
         ops.erosion_init(hm, H, W, W, erosion.height_scale, s0, W)
-        fin = ops.erosion_iterate(erosion_params(**erosion.as_dict()), s0, s1, None if fused else bufs[3], H, W, W,
-                                  erosion.iterations, fused)
+        fin = ops.erosion_iterate(erosion_params(**erosion.as_dict()), s0, s1, uvs, H, W, W, erosion.iterations, fused)
         ops.erosion_emit(fin, H, W, W, erosion.height_scale, 0, 0, H, W, uint8, hm, H, W)
         dev.sync()
         dev.d2h(out, hm, H * W * (1 if uint8 else 4))
@@ -168,10 +147,6 @@ def erode(device_ops, heightmap, erosion=None, fused=None, water=False, out=None
         if water:
             depth = np.empty(shape, np.float32)
             dev.d2h(depth, fin + plane, plane)
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
     return (out, depth) if water else out
 
 
@@ -216,8 +191,7 @@ def main(argv=None):
     x = read_image(a.input, "L", mmap=False)
     dev = Device(0)
     try:
-        res = erode(Ops(dev), x, a.erosion, fused=True if a.fused else False if a.plain else None,
-                    water=a.water is not None)
+        res = erode(Ops(dev), x, a.erosion, fused=form_choice(a.fused, a.plain), water=a.water is not None)
     finally:
         dev.close()
     hm, depth = res if a.water is not None else (res, None)

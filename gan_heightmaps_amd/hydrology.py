@@ -36,12 +36,13 @@ channel in float32, the subtraction, the product and the sum each rounded on the
 """
 import argparse
 import dataclasses
-import math
+import functools
 import sys
 
 import numpy as np
 
-from .util import is_int as _is_int, read_image
+from .planes import as_plane, check_keep, scratch
+from .util import form_choice, is_int as _is_int, is_number as _number, read_image
 
 __all__ = ["DEFAULT_TILED", "KEEP", "MAX_RIVER_WIDTH", "Water", "Hydrology", "analyse", "paint", "parse_args", "main"]
 
@@ -53,8 +54,19 @@ KEEP = ('filled', 'depth', 'direction', 'accumulation', 'basin')
 DEFAULT_TILED = True
 
 
-def _number(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+def _check_blend(paint):
+    """the part of a Water and a Road that says how marked pixels are blended: ``opacity`` in [0, 1] and ``colour``, three
+    numbers in [0, 1], checked and frozen as a float and a tuple of floats"""
+    if not _number(paint.opacity) or not 0.0 <= paint.opacity <= 1.0:
+        raise ValueError("opacity must lie in [0, 1], got %r" % (paint.opacity,))
+    try:
+        colour = tuple(paint.colour)
+    except TypeError:
+        colour = ()
+    if len(colour) != 3 or not all(_number(c) and 0.0 <= c <= 1.0 for c in colour):
+        raise ValueError("colour must be three numbers in [0, 1], got %r" % (paint.colour,))
+    object.__setattr__(paint, "opacity", float(paint.opacity))
+    object.__setattr__(paint, "colour", tuple(float(c) for c in colour))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -76,19 +88,10 @@ class Water:
             raise ValueError("river_width must be an integer in [0, %d], got %r" % (MAX_RIVER_WIDTH, self.river_width))
         if not _number(self.lake_min_depth) or not 0 <= self.lake_min_depth < 3e38:
             raise ValueError("lake_min_depth must be a finite number >= 0, got %r" % (self.lake_min_depth,))
-        if not _number(self.opacity) or not 0.0 <= self.opacity <= 1.0:
-            raise ValueError("opacity must lie in [0, 1], got %r" % (self.opacity,))
-        try:
-            colour = tuple(self.colour)
-        except TypeError:
-            colour = ()
-        if len(colour) != 3 or not all(_number(c) and 0.0 <= c <= 1.0 for c in colour):
-            raise ValueError("colour must be three numbers in [0, 1], got %r" % (self.colour,))
+        _check_blend(self)
         object.__setattr__(self, "river_threshold", int(self.river_threshold))
         object.__setattr__(self, "river_width", int(self.river_width))
         object.__setattr__(self, "lake_min_depth", float(self.lake_min_depth))
-        object.__setattr__(self, "opacity", float(self.opacity))
-        object.__setattr__(self, "colour", tuple(float(c) for c in colour))
 
 
 class Hydrology:
@@ -116,35 +119,7 @@ def _check_water(water):
     return water
 
 
-def _check_size(H, W):
-    if H < 1 or W < 1 or H * W >= 1 << 31 or H > 4 * 65535:
-        raise ValueError("heightmap size %d x %d out of range (H W < 2^31, H <= 262140)" % (H, W))
-
-
-def _as_plane(heightmap):
-    a = heightmap if hasattr(heightmap, "dtype") and hasattr(heightmap, "shape") else np.asarray(heightmap)
-    if a.ndim == 3 and a.shape[0] == 1:
-        a = a[0]
-    if a.ndim != 2:
-        raise ValueError("heightmap must be (H, W) or (1, H, W), got %s" % (tuple(a.shape),))
-    _check_size(a.shape[0], a.shape[1])                   # by shape arithmetic, before a single element is touched
-    if a.dtype == np.uint8:
-        a = np.asarray(a).astype(np.float32) / np.float32(255)
-    elif a.dtype.kind == "f":
-        a = np.ascontiguousarray(a, np.float32)
-    else:
-        raise ValueError("heightmap must be uint8 or floating point, got %s" % a.dtype)
-    if not np.isfinite(a).all():
-        raise ValueError("the heightmap has non-finite values")
-    return np.ascontiguousarray(a + np.float32(0))         # -0 -> +0, as the kernels read it
-
-
-def _check_keep(keep):
-    keep = (keep,) if isinstance(keep, str) else tuple(keep)
-    for k in keep:
-        if k not in KEEP:
-            raise ValueError("keep holds %r: the planes are %s" % (k, ", ".join(KEEP)))
-    return keep
+_as_plane = functools.partial(as_plane, raw=True)          # (route's intake too)
 
 
 def analyse(ops, heightmap, tiled=None, keep=KEEP):
@@ -152,18 +127,16 @@ def analyse(ops, heightmap, tiled=None, keep=KEEP):
     ops: a device.Ops; heightmap: (H, W) or (1, H, W), floating point and finite, or uint8; tiled: the LDS form of the two
     relaxations (True) or the plain one (False): the same bits; default DEFAULT_TILED.  keep: the planes to download.
     Returns a Hydrology."""
-    keep = _check_keep(keep)
+    keep = check_keep(keep, KEEP)
     a = _as_plane(heightmap)
     H, W = a.shape
     tiled = DEFAULT_TILED if tiled is None else bool(tiled)
     n = H * W
     dev = ops.dev
-    bufs = []
     out = {}
-    try:
-        for nbytes in (4 * n, 4 * n, 4 * n, n, 4 * n, 4 * n, ops.hydrology_workspace(H, W)):
-            bufs.append(dev.alloc(nbytes))
-        d_h, d_f, d_d, d_dir, d_a, d_b, ws = bufs
+    with scratch(dev) as alloc:
+        d_h, d_f, d_d, d_dir, d_a, d_b, ws = [alloc(nbytes) for nbytes in (4 * n, 4 * n, 4 * n, n, 4 * n, 4 * n,
+                                                                           ops.hydrology_workspace(H, W))]
         dev.h2d(d_h, a)
         fill_sweeps, _ = ops.hydrology_fill(d_h, H, W, W, tiled, d_f, W, ws)
         flat_sweeps = ops.hydrology_flats(d_f, H, W, W, tiled, d_d, W, ws)
@@ -175,10 +148,6 @@ def analyse(ops, heightmap, tiled=None, keep=KEEP):
             if name in keep or (name == 'filled' and 'depth' in keep):
                 out[name] = np.empty((H, W), dtype)
                 dev.d2h(out[name], ptr, out[name].nbytes)
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
     if 'depth' in keep:
         out['depth'] = out['filled'] - a
     if 'filled' not in keep:
@@ -217,32 +186,44 @@ def paint(ops, texture, hydro, water=None, value_range=None):
     water = _check_water(water)
     if not isinstance(hydro, Hydrology) or hydro.depth is None or hydro.accumulation is None:
         raise ValueError("hydro must be a Hydrology that kept 'depth' and 'accumulation'")
+    return _paint(ops, texture, value_range, "hydrology", hydro.shape, hydro.depth, hydro.accumulation, water.river_threshold,
+                  water.river_width, water.colour, water.opacity, water.lake_min_depth)
+
+
+def _paint(ops, texture, value_range, noun, shape, depth, marks, threshold, width, colour, opacity, lake_min_depth=0.0):
+    """the one paint, of water and of roads (route.paint): a pixel is marked where ``depth`` > lake_min_depth -- depth=None:
+    a plane of zeros, which exceeds no minimum depth of 0 -- or where the largest of ``marks`` within ``width`` pixels is >=
+    threshold, and blended towards ``colour`` with ``opacity``.  The texture's form, then its size against ``shape``
+    (the ``noun``'s), are checked before the device is read; upload, one launch, download, in the texture's own form"""
     planes, unit, u8 = _texture_planes(texture, value_range)
     C_, H, W = planes.shape
-    if (H, W) != tuple(hydro.shape):
-        raise ValueError("texture %s and hydrology %s differ in size" % ((H, W), tuple(hydro.shape)))
-    depth = np.ascontiguousarray(hydro.depth, np.float32)
-    acc = np.ascontiguousarray(hydro.accumulation, np.uint32)
+    if (H, W) != tuple(shape):
+        raise ValueError("texture %s and %s %s differ in size" % ((H, W), noun, tuple(shape)))
+    depth = np.zeros((H, W), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32)
+    marks = np.ascontiguousarray(marks, np.uint32)
     res = np.empty((C_, H, W), np.uint8 if u8 else np.float32)
     dev = ops.dev
-    bufs = []
-    try:
-        for x in (depth, acc, planes, res):
-            bufs.append(dev.alloc(x.nbytes))
-        for p, x in zip(bufs, (depth, acc, planes)):
+    with scratch(dev) as alloc:
+        bufs = [alloc(x.nbytes) for x in (depth, marks, planes, res)]
+        for p, x in zip(bufs, (depth, marks, planes)):
             dev.h2d(p, x)
-        ops.hydrology_paint(bufs[0], W, bufs[1], W, H, W, bufs[2], W, C_, texture_colour(water.colour, unit), water.opacity,
-                            water.lake_min_depth, water.river_threshold, water.river_width, u8, bufs[3], W)
+        ops.hydrology_paint(bufs[0], W, bufs[1], W, H, W, bufs[2], W, C_, texture_colour(colour, unit), opacity,
+                            lake_min_depth, threshold, width, u8, bufs[3], W)
         dev.sync()
         dev.d2h(res, bufs[3], res.nbytes)
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
     a = np.asarray(texture)
     if u8:
         return np.ascontiguousarray(res[0] if a.ndim == 2 else res.transpose(1, 2, 0))
     return res[0] if a.ndim == 2 else res
+
+
+def _save_painted(path, painted):
+    """what ``paint`` returned, as a PNG: uint8 as it is; a float texture with one channel as unit, with three as tanh"""
+    from .util import convert_to_rgb, save_png, to_uint8
+    if painted.dtype != np.uint8:
+        planes = painted[None] if painted.ndim == 2 else painted
+        painted = to_uint8(convert_to_rgb(planes, is_grayscale=planes.shape[0] == 1))
+    save_png(path, painted[:, :, 0] if painted.ndim == 3 and painted.shape[2] == 1 else painted)
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------
@@ -270,7 +251,7 @@ def parse_args(argv):
                         opacity=a.opacity)
     except ValueError as e:
         p.error(str(e))
-    a.form = True if a.tiled else False if a.plain else None
+    a.form = form_choice(a.tiled, a.plain)
     return a
 
 
@@ -289,11 +270,7 @@ def main(argv=None):
     for k in KEEP:
         np.save("%s.%s.npy" % (a.out_prefix, k), getattr(hydro, k))
     if painted is not None:
-        from .util import convert_to_rgb, save_png, to_uint8
-        if painted.dtype != np.uint8:                      # a float .npy texture: one channel is unit, three are tanh
-            planes = painted[None] if painted.ndim == 2 else painted
-            painted = to_uint8(convert_to_rgb(planes, is_grayscale=planes.shape[0] == 1))
-        save_png(a.painted, painted[:, :, 0] if painted.ndim == 3 and painted.shape[2] == 1 else painted)
+        _save_painted(a.painted, painted)
     return 0
 
 

@@ -36,15 +36,16 @@ meshes cut from tile-aligned rectangles of one world (``TerrainWorld.mesh``) agr
 import argparse
 import collections
 import dataclasses
+import functools
 import json
-import math
 import os
 import struct
 import sys
 
 import numpy as np
 
-from .util import is_int as _is_int, read_image
+from .planes import as_plane, scratch
+from .util import form_choice, is_int as _is_int, is_number as _is_number, read_image
 
 __all__ = ["DEFAULT_FUSED", "MAX_TILE", "DevicePlane", "ErrorMap", "TerrainMesh", "fit", "default_tile", "heightmap_mesh",
            "parse_args", "main"]
@@ -65,37 +66,18 @@ def _tile_log2(tile):
 
 
 def _check_error(max_error):
-    if isinstance(max_error, bool) or not isinstance(max_error, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(max_error) or max_error < 0 or not np.float32(max_error) < np.float32(3.4e38):
+    if not _is_number(max_error) or max_error < 0 or not np.float32(max_error) < np.float32(3.4e38):
         raise ValueError("max_error must be a finite number >= 0, got %r" % (max_error,))
     return float(max_error)
 
 
 def _check_scale(height_scale):
-    if isinstance(height_scale, bool) or not isinstance(height_scale, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(height_scale):
+    if not _is_number(height_scale):
         raise ValueError("height_scale must be a finite number, got %r" % (height_scale,))
     return float(height_scale)
 
 
-def _as_plane(heightmap):
-    """skylight._as_plane, with (1, H, W) accepted: what a greyscale generator returns"""
-    a = heightmap if hasattr(heightmap, "dtype") else np.asarray(heightmap)
-    if a.ndim == 3 and a.shape[0] == 1:
-        a = a[0]
-    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("heightmap must be (H, W) or (1, H, W), got %s" % (tuple(np.shape(heightmap)),))
-    if a.dtype == np.uint8:
-        a = np.asarray(a).astype(np.float32) / np.float32(255)
-    elif a.dtype.kind == "f":
-        a = np.ascontiguousarray(a, np.float32)
-        if a.size and (a.min() < 0 or a.max() > 1):
-            raise ValueError("a floating-point heightmap must lie in [0, 1]")
-    else:
-        raise ValueError("heightmap must be uint8 or floating point in [0, 1], got %s" % a.dtype)
-    if not np.isfinite(a).all():
-        raise ValueError("the heightmap has non-finite values")
-    return np.ascontiguousarray(a)
+_plane = functools.partial(as_plane, unit_range=True)
 
 
 def default_tile(rows, cols):
@@ -268,7 +250,7 @@ class ErrorMap:
     def __init__(self, ops, heightmap, tile=256, fused=None, origin=(0, 0), valid_shape=None, own=True):
         self.tile, self._k = int(tile), _tile_log2(tile)
         self.fused = DEFAULT_FUSED if fused is None else bool(fused)
-        plane = heightmap if isinstance(heightmap, DevicePlane) else _as_plane(heightmap)
+        plane = heightmap if isinstance(heightmap, DevicePlane) else _plane(heightmap)
         rows, cols = (plane.rows, plane.cols) if isinstance(plane, DevicePlane) else plane.shape
         T = self.tile
         if rows <= T or cols <= T or (rows - 1) % T or (cols - 1) % T:
@@ -345,13 +327,8 @@ class ErrorMap:
         """(V, F) of the mesh at this tolerance; nothing but the blocks' sums is written"""
         self._open()
         tol, rect = _check_error(max_error), self._rect(rect)
-        dev = self._dev
-        ws = dev.alloc(self._ops.mesh_workspace(rect[2], rect[3]))
-        try:
-            return self._count(tol, rect, ws)
-        finally:
-            dev.sync()
-            dev.free(ws)
+        with scratch(self._dev) as alloc:
+            return self._count(tol, rect, alloc(self._ops.mesh_workspace(rect[2], rect[3])))
 
     def extract(self, max_error, rect=None):
         """the mesh at this tolerance as a TerrainMesh; rect = (y0, x0, h, w): the tiles [y0, y0 + h] x [x0, x0 + w] of the
@@ -360,12 +337,9 @@ class ErrorMap:
         tol, rect = _check_error(max_error), self._rect(rect)
         y0, x0, h, w = rect
         dev, ops = self._dev, self._ops
-        bufs = []
-
-        def alloc(n):
-            bufs.append(dev.alloc(max(int(n), 4)))
-            return bufs[-1]
-        try:
+        with scratch(dev) as scr:
+            def alloc(n):                                         # (an empty mesh still gets pointers)
+                return scr(max(int(n), 4))
             ws = alloc(ops.mesh_workspace(h, w))
             V, F = self._count(tol, rect, ws)
             grid, heights, tris = np.empty((V, 2), np.int32), np.empty(V, np.float32), np.empty((F, 3), np.uint32)
@@ -376,10 +350,6 @@ class ErrorMap:
             for host, ptr in ((grid, d_grid), (heights, d_heights), (tris, d_tris)):
                 if host.nbytes:
                     dev.d2h(host, ptr, host.nbytes)
-        finally:
-            dev.sync()
-            for p in bufs:
-                dev.free(p)
         vh, vw = self.valid_shape
         valid = (max(1, min(h + 1, vh - y0)), max(1, min(w + 1, vw - x0)))
         return TerrainMesh(grid, heights, tris, (h + 1, w + 1), (self.origin[0] + y0, self.origin[1] + x0), self.tile, tol,
@@ -390,7 +360,7 @@ def heightmap_mesh(ops, heightmap, max_error, tile=None, fused=None):
     """fit, build the error map and extract: the mesh of a heightmap of any size.  heightmap: (H, W) or (1, H, W), uint8 or
     floating point in [0, 1]; tile: None means default_tile(H, W)"""
     tol = _check_error(max_error)
-    a = _as_plane(heightmap)
+    a = _plane(heightmap)
     tile = default_tile(*a.shape) if tile is None else tile
     plane, valid = fit(a, tile)
     with ErrorMap(ops, plane, tile=tile, fused=fused, valid_shape=valid) as em:
@@ -437,7 +407,7 @@ def main(argv=None):
     tex = None if a.texture is None else np.ascontiguousarray(read_image(a.texture, "RGB", mmap=False))
     dev = Device(0)
     try:
-        m = heightmap_mesh(Ops(dev), x, a.max_error, tile=a.tile, fused=True if a.fused else False if a.plain else None)
+        m = heightmap_mesh(Ops(dev), x, a.max_error, tile=a.tile, fused=form_choice(a.fused, a.plain))
     finally:
         dev.close()
     m.save(a.output, texture=tex, height_scale=a.height_scale)

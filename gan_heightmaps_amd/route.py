@@ -47,8 +47,9 @@ import sys
 import numpy as np
 
 from . import hydrology as _hy
-from .hydrology import MAX_RIVER_WIDTH, _as_plane, _number
-from .util import is_int as _is_int, read_image
+from .hydrology import MAX_RIVER_WIDTH, _as_plane
+from .planes import check_keep, scratch
+from .util import form_choice, is_int as _is_int, is_number as _number, read_image
 
 __all__ = ["DEFAULT_TILED", "KEEP", "UNIT", "MAX_WEIGHT", "UNREACHED", "NO_PARENT", "MAX_SOURCES", "Travel", "Road", "CostField",
            "field", "paint", "raster", "parse_args", "main"]
@@ -84,7 +85,7 @@ class Travel:
             if not _number(v) or not 0 < v < 3e38 or not 1.0 / v < 3e38:           # 1 / grade is a float32 on the device
                 raise ValueError("%s must be a positive finite number, got %r" % (name, v))
         v = self.lake
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or math.isnan(v) or not v >= 1:
+        if not _number(v, finite=False) or math.isnan(v) or not v >= 1:
             raise ValueError("lake must be a number >= 1 (inf: impassable), got %r" % (v,))
         if not _number(self.ford) or not 1 <= self.ford < 3e38:
             raise ValueError("ford must be a finite number >= 1, got %r" % (self.ford,))
@@ -110,20 +111,11 @@ class Road:
     def __post_init__(self):
         if not _is_int(self.width) or not 0 <= self.width <= MAX_RIVER_WIDTH:
             raise ValueError("width must be an integer in [0, %d], got %r" % (MAX_RIVER_WIDTH, self.width))
-        if not _number(self.opacity) or not 0.0 <= self.opacity <= 1.0:
-            raise ValueError("opacity must lie in [0, 1], got %r" % (self.opacity,))
-        try:
-            colour = tuple(self.colour)
-        except TypeError:
-            colour = ()
-        if len(colour) != 3 or not all(_number(c) and 0.0 <= c <= 1.0 for c in colour):
-            raise ValueError("colour must be three numbers in [0, 1], got %r" % (self.colour,))
+        _hy._check_blend(self)
         t = self.traffic_threshold
         if t is not None and (not _is_int(t) or not 1 <= t < 1 << 32):
             raise ValueError("traffic_threshold must be None or an integer in [1, 2^32), got %r" % (t,))
         object.__setattr__(self, "width", int(self.width))
-        object.__setattr__(self, "opacity", float(self.opacity))
-        object.__setattr__(self, "colour", tuple(float(c) for c in colour))
         object.__setattr__(self, "traffic_threshold", None if t is None else int(t))
 
 
@@ -220,14 +212,6 @@ def _check_road(road):
     return road
 
 
-def _check_keep(keep):
-    keep = (keep,) if isinstance(keep, str) else tuple(keep)
-    for k in keep:
-        if k not in KEEP:
-            raise ValueError("keep holds %r: the planes are %s" % (k, ", ".join(KEEP)))
-    return keep
-
-
 def _check_sources(sources, H, W, origin=(0, 0)):
     """-> ([(row, col)] as given, int32 flat indices inside the plane)"""
     try:
@@ -282,7 +266,7 @@ def field(ops, heightmap, sources, travel=None, hydro=None, penalty=None, tiled=
     ``field(ops, hydro.filled, towns, hydro=hydro)``; penalty: a float plane, >= 1 or inf (impassable); tiled: the LDS form of the
     relaxation (True) or the plain one (False): the same bits; default DEFAULT_TILED.  keep: the planes to return.  origin: the
     coordinates of cell [0, 0], in which ``sources`` are given and paths come back.  Returns a CostField."""
-    keep = _check_keep(keep)
+    keep = check_keep(keep, KEEP)
     travel = _check_travel(travel)
     a = _as_plane(heightmap)
     H, W = a.shape
@@ -301,17 +285,15 @@ def field(ops, heightmap, sources, travel=None, hydro=None, penalty=None, tiled=
     n = H * W
     graph = 'territory' in keep or 'traffic' in keep
     dev = ops.dev
-    bufs = {}
     out = {}
-    try:
+    with scratch(dev) as alloc:
         sizes = dict(h=4 * n, cost=4 * n, parent=n, ws=ops.route_workspace(H, W))
         for name, x in (('pen', pen), ('depth', depth), ('acc', acc)):
             if x is not None:
                 sizes[name] = x.nbytes
         if graph:
             sizes.update(traffic=4 * n, basin=4 * n, hws=ops.hydrology_workspace(H, W))
-        for name, nbytes in sizes.items():
-            bufs[name] = dev.alloc(nbytes)
+        bufs = {name: alloc(nbytes) for name, nbytes in sizes.items()}
         for name, x in (('h', a), ('pen', pen), ('depth', depth), ('acc', acc)):
             if x is not None:
                 dev.h2d(bufs[name], x)
@@ -328,10 +310,6 @@ def field(ops, heightmap, sources, travel=None, hydro=None, penalty=None, tiled=
             if wanted:
                 out[name] = np.empty((H, W), dtype)
                 dev.d2h(out[name], bufs[name], out[name].nbytes)
-    finally:
-        dev.sync()
-        for p in bufs.values():
-            dev.free(p)
     if graph:
         out['territory'], out['traffic'] = territory_traffic(out.pop('basin'), out['traffic'], out['cost'], flat)
     planes = {k: out[k] for k in keep}
@@ -351,34 +329,11 @@ def paint(ops, texture, cost_field, paths=(), road=None, value_range=None):
     if road.traffic_threshold is not None:
         if cost_field.traffic is None:
             raise ValueError("road.traffic_threshold needs a CostField that kept 'traffic'")
-        marks, threshold = np.ascontiguousarray(cost_field.traffic, np.uint32), road.traffic_threshold
+        marks, threshold = cost_field.traffic, road.traffic_threshold
     else:
         marks, threshold = raster((H, W), paths, cost_field.origin), 1
-    planes, unit, u8 = _hy._texture_planes(texture, value_range)
-    C_ = planes.shape[0]
-    if tuple(planes.shape[1:]) != (H, W):
-        raise ValueError("texture %s and cost field %s differ in size" % (tuple(planes.shape[1:]), (H, W)))
-    depth = np.zeros((H, W), np.float32)                   # no lakes: nothing exceeds a minimum depth of 0
-    res = np.empty((C_, H, W), np.uint8 if u8 else np.float32)
-    dev = ops.dev
-    bufs = []
-    try:
-        for x in (depth, marks, planes, res):
-            bufs.append(dev.alloc(x.nbytes))
-        for p, x in zip(bufs, (depth, marks, planes)):
-            dev.h2d(p, x)
-        ops.hydrology_paint(bufs[0], W, bufs[1], W, H, W, bufs[2], W, C_, _hy.texture_colour(road.colour, unit), road.opacity,
-                            0.0, threshold, road.width, u8, bufs[3], W)
-        dev.sync()
-        dev.d2h(res, bufs[3], res.nbytes)
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
-    a = np.asarray(texture)
-    if u8:
-        return np.ascontiguousarray(res[0] if a.ndim == 2 else res.transpose(1, 2, 0))
-    return res[0] if a.ndim == 2 else res
+    return _hy._paint(ops, texture, value_range, "cost field", (H, W), None, marks, threshold, road.width, road.colour,
+                      road.opacity)                        # no lakes: a depth of zeros and a minimum depth of 0
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------
@@ -427,7 +382,7 @@ def parse_args(argv):
         a.road = Road(width=a.road_width, traffic_threshold=a.traffic_threshold)
     except ValueError as e:
         p.error(str(e))
-    a.form = True if a.tiled else False if a.plain else None
+    a.form = form_choice(a.tiled, a.plain)
     return a
 
 
@@ -450,11 +405,7 @@ def main(argv=None):
     for i, path in enumerate(paths):
         np.save("%s.path%d.npy" % (a.out_prefix, i), path)
     if painted is not None:
-        from .util import convert_to_rgb, save_png, to_uint8
-        if painted.dtype != np.uint8:                      # a float .npy texture: one channel is unit, three are tanh
-            planes = painted[None] if painted.ndim == 2 else painted
-            painted = to_uint8(convert_to_rgb(planes, is_grayscale=planes.shape[0] == 1))
-        save_png(a.painted, painted[:, :, 0] if painted.ndim == 3 and painted.shape[2] == 1 else painted)
+        _hy._save_painted(a.painted, painted)
     return 0
 
 

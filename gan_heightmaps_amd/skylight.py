@@ -25,12 +25,12 @@ holds ``reach`` more pixels all round (``margin``); without them the plane is cl
 import argparse
 import dataclasses
 import functools
-import math
 import sys
 
 import numpy as np
 
-from .util import is_int as _is_int, read_image
+from .planes import as_plane, check_size, scratch
+from .util import form_choice, is_int as _is_int, is_number as _number, read_image
 
 __all__ = ["DEFAULT_TILED", "MAX_DIRECTIONS", "MAX_STEPS", "SkyLight", "bake", "bake_device", "parse_args", "main"]
 
@@ -41,10 +41,6 @@ MAX_STEPS = 256              # GHM_SKYLIGHT_MAX_STEPS
 DEFAULT_TILED = True
 # one table entry as the kernels read it: ghm_skylight_sample (include/ghm.h)
 SAMPLE_DTYPE = np.dtype([("iy", np.int32), ("ix", np.int32), ("wy", np.float32), ("wx", np.float32), ("inv_r", np.float32)])
-
-
-def _number(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -106,19 +102,7 @@ def _check_scale(height_scale):
     return float(height_scale)
 
 
-def _as_plane(heightmap):
-    a = heightmap if hasattr(heightmap, "dtype") else np.asarray(heightmap)
-    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("heightmap must be (H, W), got %s" % (tuple(np.shape(heightmap)),))
-    if a.dtype == np.uint8:
-        a = np.asarray(a).astype(np.float32) / np.float32(255)
-    elif a.dtype.kind == "f":
-        a = np.ascontiguousarray(a, np.float32)
-    else:
-        raise ValueError("heightmap must be uint8 or floating point in [0, 1], got %s" % a.dtype)
-    if not np.isfinite(a).all():
-        raise ValueError("the heightmap has non-finite values")
-    return np.ascontiguousarray(a)
+_plane = functools.partial(as_plane, lead=False)
 
 
 def use_tiled(ops, sky, tiled):
@@ -148,31 +132,24 @@ def bake(ops, heightmap, sky=None, height_scale=64.0, margin=0, out=None, uint8=
     if not _is_int(margin) or margin < 0:
         raise ValueError("margin must be an integer >= 0, got %r" % (margin,))
     margin = int(margin)
-    a = _as_plane(heightmap)
+    a = _plane(heightmap)
     rows, cols = a.shape
     H, W = rows - 2 * margin, cols - 2 * margin
     if H < 1 or W < 1:
         raise ValueError("a heightmap of %d x %d has no interior inside a margin of %d" % (rows, cols, margin))
-    if rows * cols >= 1 << 31 or H > 4 * 65535:
-        raise ValueError("heightmap size %d x %d out of range" % (rows, cols))
+    check_size(H, W, plane=(rows, cols))
     dtype = np.uint8 if uint8 else np.float32
     if out is None:
         out = np.empty((H, W), dtype)
     elif not isinstance(out, np.ndarray) or out.shape != (H, W) or out.dtype != dtype or not out.flags['C_CONTIGUOUS']:
         raise ValueError("out must be a contiguous %s %s, got %s" % (np.dtype(dtype), (H, W), getattr(out, "shape", out)))
     dev = ops.dev
-    bufs = []
-    try:
-        bufs.append(dev.alloc(a.nbytes))
-        bufs.append(dev.alloc(out.nbytes))
-        dev.h2d(bufs[0], a)
-        bake_device(ops, bufs[0], rows, cols, sky, height_scale, bufs[1], margin=margin, uint8=uint8, tiled=tiled)
+    with scratch(dev) as alloc:
+        src, dst = alloc(a.nbytes), alloc(out.nbytes)
+        dev.h2d(src, a)
+        bake_device(ops, src, rows, cols, sky, height_scale, dst, margin=margin, uint8=uint8, tiled=tiled)
         dev.sync()
-        dev.d2h(out, bufs[1], out.nbytes)
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
+        dev.d2h(out, dst, out.nbytes)
     return out
 
 
@@ -207,8 +184,7 @@ def main(argv=None):
     dev = Device(0)
     try:
         to_png = not a.output.endswith(".npy")
-        res = bake(Ops(dev), x, a.sky, height_scale=a.height_scale, uint8=to_png,
-                   tiled=True if a.tiled else False if a.plain else None)
+        res = bake(Ops(dev), x, a.sky, height_scale=a.height_scale, uint8=to_png, tiled=form_choice(a.tiled, a.plain))
     finally:
         dev.close()
     if to_png:

@@ -30,6 +30,7 @@ import sys
 
 import numpy as np
 
+from .planes import scratch
 from .util import is_int as _is_int
 
 __all__ = ["PATCH", "MAX_CHANNELS", "SWD", "Descriptors", "distance", "compare", "corners", "directions", "header", "row",
@@ -195,14 +196,12 @@ class Descriptors:
     def stats(self, level, workspace):
         """float32 [C, 2] (mean, population standard deviation) of a level's channels; ValueError on a deviation of 0"""
         if level not in self._stats:
-            st = self.dev.alloc(8 * self.C)
-            try:
+            with scratch(self.dev, sync=False) as alloc:
+                st = alloc(8 * self.C)
                 self.ops.swd_stats(self.desc[level], self.N, self.C, st, workspace)
                 self.dev.sync()
                 out = np.zeros((self.C, 2), np.float32)
                 self.dev.d2h(out, st, out.nbytes)
-            finally:
-                self.dev.free(st)
             for c in range(self.C):
                 if not out[c, 1] > 0:
                     raise ValueError("set %d, level %d, channel %d: the standard deviation of the descriptors is 0 (a constant "
@@ -253,11 +252,9 @@ def distance(ops, a, b, max_mb=None, sort_chunk=0):
     dev = ops.dev
     for d in {id(x): x for x in (a.dev, b.dev, dev)}.values():
         d.sync()                                                # the sets may have been filled on other streams
-    bufs, vals = [], []
-    try:
-        for n in (4 * D * N, 4 * D * N, 4 * K * D, 8 * C, 8 * C, ops.swd_workspace()):
-            bufs.append(dev.alloc(n))
-        pa, pb, dirs, sa, sb, ws = bufs
+    vals = []
+    with scratch(dev) as alloc:
+        pa, pb, dirs, sa, sb, ws = [alloc(n) for n in (4 * D * N, 4 * D * N, 4 * K * D, 8 * C, 8 * C, ops.swd_workspace())]
         for level in range(a.L):
             dev.h2d(sa, a.stats(level, ws))
             dev.h2d(sb, b.stats(level, ws))
@@ -269,10 +266,6 @@ def distance(ops, a, b, max_mb=None, sort_chunk=0):
                     ops.swd_sort_columns(out, N, D, sort_chunk)
                 per.append(ops.swd_l1(pa, pb, D * N, ws))      # (waits for the stream: dirs may be overwritten)
             vals.append(1e3 * (sum(per) / len(per)))
-    finally:
-        dev.sync()
-        for p in bufs:
-            dev.free(p)
     return {"levels": [min(h, w) for h, w in a.sizes], "swd": vals, "mean": float(np.mean(vals))}
 
 

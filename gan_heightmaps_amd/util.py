@@ -5,6 +5,7 @@ Everything here is numpy on what the device has already produced; PNGs are writt
 reference's skimage is not in this image): a float image in [0,1] becomes uint8 by round(255*x), which is
 what skimage.io.imsave does for float input.
 """
+import math
 import os
 
 import numpy as np
@@ -87,6 +88,18 @@ def imread(fname):
 
 def is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def is_number(v, finite=True):
+    """a real number, Python's or numpy's, and no bool; finite, unless ``finite`` is False"""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) \
+        and (not finite or math.isfinite(v))
+
+
+def form_choice(first, second):
+    """a command line's pair of exclusive switches (--tiled | --plain, --fused | --plain) as a ``tiled=`` / ``fused=``
+    argument: True, False, or None where neither was given (the module's default)"""
+    return True if first else False if second else None
 
 
 def read_image(path, mode=None, mmap=True):

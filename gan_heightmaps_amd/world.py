@@ -52,7 +52,8 @@ from .streaming import DownloadRing, check_uint8_channels, output_array, shift_a
 from .terrain import BLENDS, INT32_LIMIT, TerrainGeometry
 from . import terrain as _terrain
 from .texture import check_overlap
-from .util import is_int as _is_int
+from .planes import scratch
+from .util import is_int as _is_int, is_number as _is_number
 
 __all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "SKY_SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
            "window_elements", "default_chunk_cells", "slot_batches", "erosion_sources", "snap_out", "plan_windows", "TerrainWorld",
@@ -304,20 +305,13 @@ class _SceneSinks:
 
 @contextlib.contextmanager
 def _flagged_planes(dev, sizes, sync):
-    """device planes of ``sizes`` bytes for requests through _SceneSinks and, last, their int32 flag, zeroed: one list, to
-    which the body may add.  What it holds when the body ends, or fails, is freed; sync: once the device is idle"""
-    bufs = []
-    try:
-        for n in sizes + (4,):
-            bufs.append(dev.alloc(n))
+    """device planes of ``sizes`` bytes for requests through _SceneSinks and, last, their int32 flag, zeroed, in a
+    planes.scratch(dev, sync): -> [the allocator, the planes ..., the flag]"""
+    with scratch(dev, sync) as alloc:
+        bufs = [alloc(n) for n in sizes + (4,)]
         dev.memset_zero(bufs[-1], 4)
         dev.sync()
-        yield bufs
-    finally:
-        if sync:
-            dev.sync()
-        for p in bufs:
-            dev.free(p)
+        yield [alloc] + bufs
 
 
 class TerrainWorld:
@@ -334,7 +328,7 @@ class TerrainWorld:
             raise ValueError("blend must be one of %s, got %r" % (BLENDS, blend))
         if not _is_int(batch_size) or not 1 <= batch_size <= MAX_BATCH:
             raise ValueError("batch_size must be an integer in [1, %d], got %r" % (MAX_BATCH, batch_size))
-        if isinstance(cache_mb, bool) or not isinstance(cache_mb, (int, float, np.integer, np.floating)) or cache_mb < 0:
+        if not _is_number(cache_mb, finite=False) or cache_mb < 0:
             raise ValueError("cache_mb must be a number >= 0, got %r" % (cache_mb,))
         if latent_fn is not None and not callable(latent_fn):
             raise ValueError("latent_fn must be callable as latent_fn(i, j)")
@@ -626,19 +620,18 @@ class TerrainWorld:
             raise ValueError("this TerrainWorld is closed")
         dev = self.model.device
         margin = 0 if sky is None else sky.reach
-        with _flagged_planes(dev, (4 * h * w, 12 * h * w), sync=False) as bufs:    # the height plane, three texture planes
-            hm, tex, flag = bufs
+        # the height plane, three texture planes
+        with _flagged_planes(dev, (4 * h * w, 12 * h * w), sync=False) as (alloc, hm, tex, flag):
             requests, grown = [((y0, x0, h, w), hm, tex)], None
             if sky is not None:
                 # the height plane of the grown rectangle: the same chunks, mapped as the scene's own plane is
                 gh, gw = h + 2 * margin, w + 2 * margin
                 if gh * gw >= 1 << 31:
                     raise ValueError("the scene grown by the sky's reach, %d x %d, is beyond 2^31 pixels" % (gh, gw))
-                grown = dev.alloc(4 * gh * gw)
-                bufs.append(grown)
+                grown = alloc(4 * gh * gw)
                 requests.insert(0, ((y0 - margin, x0 - margin, gh, gw), grown, None))
             self._fill_planes(dev, requests, flag, "the heightmap or the texture has")
-            bufs[:] = [flag]                                      # the planes are the scene's from here
+            alloc.keep(tex, *(plane for _, plane, _ in requests))    # all but the flag is the scene's from here
         return Scene.from_device(dev, hm, tex, h, w, origin=(y0, x0), sky=sky, sky_src=grown, margin=margin, **kw)
 
     def mesh(self, y0, x0, h, w, max_error, tile=256, texture=False, fused=None):
@@ -666,7 +659,7 @@ class TerrainWorld:
             raise ValueError("the region grown by a ring of tiles, %d x %d, is at or beyond 2^31 vertices" % (gh, gw))
         gy, gx, gh, gw = self._check_region(y0 - tile, x0 - tile, gh, gw)
         self._bind()
-        with _flagged_planes(self._dev, (4 * gh * gw,), sync=True) as (grown, flag):
+        with _flagged_planes(self._dev, (4 * gh * gw,), sync=True) as (_, grown, flag):
             self._fill_planes(self._dev, [((gy, gx, gh, gw), grown, None)], flag, "the heightmap has")
             with _mesh.ErrorMap(self._ops, _mesh.DevicePlane(grown, gh, gw), tile=tile, fused=fused, origin=(gy, gx),
                                 own=False) as em:
@@ -719,8 +712,7 @@ class TerrainWorld:
         (SKY_SCENE_BYTES_PER_PIXEL: the 22 and the baked plane's 4).  The height plane grown by sky.reach that a window's bake
         reads is transient -- allocated before the bake, freed after it -- and outside this budget."""
         bpp = SCENE_BYTES_PER_PIXEL if _check_sky(sky) is None else SKY_SCENE_BYTES_PER_PIXEL
-        if isinstance(window_mb, bool) or not isinstance(window_mb, (int, float, np.integer, np.floating)) \
-                or not window_mb > 0:
+        if not _is_number(window_mb, finite=False) or not window_mb > 0:
             raise ValueError("window_mb must be a number > 0, got %r" % (window_mb,))
         snap = self._geo.out if snap is None else snap
         return plan_windows([c.footprint(max_dist) for c in cameras], snap, int(window_mb * (1 << 20)) // bpp)

@@ -104,6 +104,30 @@ def test_refusals_before_the_device_is_touched():
             RT.paint(ops, bad, cf)
 
 
+def test_both_paints_make_one_launch_with_the_arguments_they_always_sent():
+    """hydrology.paint and route.paint on a device of fake addresses (they encode the order and the sizes of the four
+    allocations) and recording ops: one hydrology_paint call each, its arguments the literals recorded from the two paints
+    as they were before they shared one"""
+    from tests.fake_device import FakeDevice, RecordingOps
+    hydro = HY.Hydrology((8, 9), (1, 1), 1, False, depth=np.zeros((8, 9), np.float32), accumulation=np.ones((8, 9), np.uint32))
+    cf = RT.CostField((8, 9), [(1, 2)], traffic=np.ones((8, 9), np.uint32))
+    path = np.array([[0, 0], [1, 1], [2, 1]], np.int32)
+    water, road = (0.12999999523162842, 0.28999999165534973, 0.44999998807907104), (0.3499999940395355, 0.30000001192092896, 0.25)
+    for tex, C, u8, out_ptr in ((np.zeros((8, 9, 3), np.uint8), 3, True, 1051392), (np.zeros((8, 9), np.float32), 1, False, 1050880)):
+        head = (1048576, 9, 1049344, 9, 8, 9, 1050112, 9, C)
+        for paint, args, want in (
+                (HY.paint, (hydro, HY.Water(river_threshold=5, river_width=2, lake_min_depth=0.25, opacity=0.5)),
+                 head + (water, 0.5, 0.25, 5, 2, u8, out_ptr, 9)),
+                (RT.paint, (cf, [path], RT.Road(width=3)), head + (road, 0.9, 0.0, 1, 3, u8, out_ptr, 9)),
+                (RT.paint, (cf, (), RT.Road(width=0, opacity=0.25, traffic_threshold=7)),
+                 head + (road, 0.25, 0.0, 7, 0, u8, out_ptr, 9))):
+            ops = RecordingOps(FakeDevice())
+            out = paint(ops, tex, *args)
+            assert ops.calls == [("hydrology_paint", want, {})], (paint.__module__, tex.dtype)
+            assert ops.dev.uploads == 3 and (out.dtype, out.shape) == (tex.dtype, tex.shape)
+            assert all(type(v) is type(w) for v, w in zip(ops.calls[0][1], want))      # 1 is not True, 0.0 is not 0
+
+
 def hand_field(origin=(0, 0)):
     """a 3 x 4 field by hand: the source at (1, 1), the last column unreached"""
     parent = np.array([[3, 4, 5, -2], [2, -1, 6, -2], [1, 0, 7, -2]], np.int8)
