@@ -447,7 +447,9 @@ __global__ __launch_bounds__(256) void smallk_dgrad_kernel(const SmallKDgradArgs
     const float* dyb = a.dy + (long)n * a.y_nstride;
     const float* wc = a.wp + (long)c * a.kh * a.kw * a.K;
     const int HoWo = a.Ho * a.Wo;
-    float s = a.bias ? a.bias[c] : 0.f;
+    // (the bias is added AFTER the products: a chain that starts at the bias rounds every step at the magnitude of
+    // bias + partial sum -- measured 12.5 x 2^-24 (sum |a||b| + |bias|) from the float64 answer on 25 taps, 4.0 this way)
+    float s = 0.f;
     for (int ta = 0; ta < a.kh; ++ta) {
         const int yy = u + a.pad - ta;
         if (yy < 0 || yy % a.stride) continue;
@@ -462,6 +464,7 @@ __global__ __launch_bounds__(256) void smallk_dgrad_kernel(const SmallKDgradArgs
             for (int k = 0; k < a.K; ++k) s = fmaf(dyb[(long)k * HoWo + i * a.Wo + j], w[k], s);
         }
     }
+    if (a.bias) s += a.bias[c];
     float* o = a.dx + (long)n * a.x_nstride + (long)c * HW + rem;
     if (a.accumulate) s += *o;
     s = ghm_act(s, a.act, a.alpha);
@@ -472,7 +475,7 @@ __global__ __launch_bounds__(256) void smallk_dgrad_kernel(const SmallKDgradArgs
 // K == 1 (d_out, pd_out): the taps of dy a dx pixel sees are the same for every input channel, so a thread owns one pixel
 // and CG consecutive channels (blockIdx.y = channel group: the weights are wave-uniform scalar loads): the tap decode and
 // the dy loads are paid once per CG outputs instead of once per output.  Same products in the same order as
-// smallk_dgrad_kernel (taps row-major, fmaf chain from the bias): bit-identical.  pd_out at 512^2, batch 8 (C512 32x32 k3
+// smallk_dgrad_kernel (taps row-major, one fmaf chain, then the bias): bit-identical.  pd_out at 512^2, batch 8 (C512 32x32 k3
 // s2): 55 -> 18 us; it sits at the turn-around of the pix2pix stage stream, where nothing of that stage runs beside it.
 template <int KS, int CG>
 __global__ __launch_bounds__(256) void smallk1_dgrad_kernel(const SmallKDgradArgs a) {
@@ -501,9 +504,10 @@ __global__ __launch_bounds__(256) void smallk1_dgrad_kernel(const SmallKDgradArg
         const int c = c0 + cc;
         if (c >= a.C) break;
         const float* wc = a.wp + (long)c * KS * KS;
-        float s = a.bias ? a.bias[c] : 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int t = 0; t < KS * KS; ++t) s = fmaf(dv[t], wc[t], s);      // (a tap outside the image adds +0: dv = 0)
+        if (a.bias) s += a.bias[c];
         float* o = a.dx + (long)n * a.x_nstride + (long)c * HW + rem;
         if (a.accumulate) s += *o;
         s = ghm_act(s, a.act, a.alpha);
@@ -2220,7 +2224,7 @@ int ghm_conv2d_fwd(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, const f
                    float* y, int32_t act, float alpha, int32_t accumulate) {
     if (int e = check_desc(d)) return e;
     GHM_CHECK(!(accumulate && act != GHM_ACT_LINEAR), "accumulate needs a linear epilogue");
-    if (d->C <= 4 && thin_fanout_fwd_ok(d, act)) return thin_fanout_fwd(ctx, d, x, wp, bias, y, act, alpha, accumulate);
+    if (d->C <= 4 && thin_fanout_fwd_ok(d, act, y)) return thin_fanout_fwd(ctx, d, x, wp, bias, y, act, alpha, accumulate);
     if (d->K <= 4 && thin_fanin_s1_fwd_ok(d)) return thin_fanin_s1_fwd(ctx, d, x, wp, bias, y, act, alpha, accumulate);
     if (taps_as_rows(d, d->K)) {
         const int T = d->kh * d->kw;
@@ -2299,9 +2303,10 @@ struct DactArg {
     float alpha;
 };
 
-static bool smallk_dgrad_ok(const ghm_conv_desc* d) {
+// (dx: the output the call was given -- where the fan-out kernel's vector stores cannot take it, this kernel serves the layer)
+static bool smallk_dgrad_ok(const ghm_conv_desc* d, const float* dx = nullptr) {
     return d->K <= 4 && d->C > 4 && GHM_OPT("GHM_NO_SMALLK_DGRAD") == nullptr &&
-           !(d->K <= 4 && thin_fanout_dgrad_ok(d, GHM_ACT_LINEAR)) && !thin_fanin_s2_ok(d, nullptr);
+           !(d->K <= 4 && thin_fanout_dgrad_ok(d, GHM_ACT_LINEAR, dx)) && !thin_fanin_s2_ok(d, nullptr);
 }
 
 static int launch_smallk_dgrad(ghm_ctx* ctx, const ghm_conv_desc* d, const float* dy, const float* wp, const float* bias,
@@ -2402,11 +2407,11 @@ int ghm_conv2d_dgrad(ghm_ctx* ctx, const ghm_conv_desc* d, const float* dy, cons
                      float* dx, int32_t act, float alpha, int32_t accumulate) {
     if (int e = check_desc(d)) return e;
     GHM_CHECK(!(accumulate && act != GHM_ACT_LINEAR), "accumulate needs a linear epilogue");
-    if (d->K <= 4 && thin_fanout_dgrad_ok(d, act))
+    if (d->K <= 4 && thin_fanout_dgrad_ok(d, act, dx))
         return thin_fanout_dgrad(ctx, d, dy, wp, bias, dx, act, alpha, accumulate);
     if (thin_fanin_s2_ok(d, dx)) return thin_fanin_s2(ctx, d, dy, wp, bias, dx, act, alpha, accumulate);
     if (d->C <= 4 && thin_fanin_s1_dgrad_ok(d)) return thin_fanin_s1_dgrad(ctx, d, dy, wp, bias, dx, act, alpha, accumulate);
-    if (smallk_dgrad_ok(d)) return launch_smallk_dgrad(ctx, d, dy, wp, bias, dx, act, alpha, accumulate, nullptr, 0, 0, 0.f);
+    if (smallk_dgrad_ok(d, dx)) return launch_smallk_dgrad(ctx, d, dy, wp, bias, dx, act, alpha, accumulate, nullptr, 0, 0, 0.f);
     if (taps_as_rows(d, d->C)) {
         const int T = d->kh * d->kw;
         void* ws = nullptr;
@@ -2600,7 +2605,7 @@ int ghm_conv2d_dgrad_t(ghm_ctx* ctx, const ghm_conv_desc* d, const float* dy, co
     const int padT = d->kh - 1 - d->pad;
     if (d->K <= 4) {
         const ghm_conv_desc sw = swapped_desc(d);
-        if (thin_fanout_fwd_ok(&sw, act)) return thin_fanout_fwd(ctx, &sw, dy, wpT, bias, dx, act, alpha, accumulate);
+        if (thin_fanout_fwd_ok(&sw, act, dx)) return thin_fanout_fwd(ctx, &sw, dy, wpT, bias, dx, act, alpha, accumulate);
     }
     if (d->kh == d->kw && d->Ho == d->H && d->Wo == d->W) {
         const PatchPlan pl = plan_patch(d->N, d->K, d->H, d->W, d->C, d->kh, ctx->num_cu);

@@ -536,10 +536,17 @@ bool thin_fanout_pool_q_ok(const ghm_conv_desc* d) { return fanout_wave_split() 
 static bool thin_enabled() { return GHM_OPT("GHM_NO_THIN") == nullptr; }
 static bool fanout_act_ok(int act) { return act == GHM_ACT_LINEAR || act == GHM_ACT_RELU || act == GHM_ACT_LRELU; }
 
+// the epilogue stores NS * 4-byte vectors (NS of fanout_plan) at out + n * out_nstride + ...: the pointer and the sample stride
+// must be multiples of that.  A null pointer passes (the host-only queries, a q-only launch).
+static bool fanout_out_aligned(int rows_out, const void* out, long out_nstride) {
+    const int ns = rows_out <= 64 ? 4 : 2;
+    return (uintptr_t)out % (ns * sizeof(float)) == 0 && out_nstride % ns == 0;
+}
+
 // forward conv with <= 4 input channels
-bool thin_fanout_fwd_ok(const ghm_conv_desc* d, int act) {
+bool thin_fanout_fwd_ok(const ghm_conv_desc* d, int act, const float* y) {
     return thin_enabled() && fanout_act_ok(act) && (long)d->N * d->Ho * d->Wo >= 32768 && (long)d->C * d->H * d->W < (1L << 30) &&
-           fanout_geometry_ok(d->K, d->C, d->kh, d->kw, d->stride, d->Ho, d->Wo);
+           fanout_geometry_ok(d->K, d->C, d->kh, d->kw, d->stride, d->Ho, d->Wo) && fanout_out_aligned(d->K, y, d->y_nstride);
 }
 
 int thin_fanout_fwd(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, const float* wp, const float* bias,
@@ -547,6 +554,7 @@ int thin_fanout_fwd(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, const 
     FanoutArgs a;
     memset(&a, 0, sizeof(a));
     const int T = d->kh * d->kw;
+    GHM_CHECK(fanout_out_aligned(d->K, y, d->y_nstride), "thin forward: output pointer / sample stride not aligned to its vector stores");
     GHM_CHECK(!yq || (d->K % 8 == 0 && ((uintptr_t)yq & 15) == 0 && (q_dt == GHM_DTYPE_BF16 || q_dt == GHM_DTYPE_F16 || q_dt == 3 || q_dt == 4)),
               "thin forward with a q output: filters %% 8 == 0, 16-byte aligned q tensor, bf16 / f16");
     a.out_q = (uint2*)yq; a.out_q_nstride = yq_nstride; a.q_dt = q_dt;
@@ -566,7 +574,9 @@ int thin_fanout_fwd(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, const 
 }
 
 // forward conv with <= 4 input channels + activation + 2x2 max-pool, fused (64 filters, stride 1, 'same')
-bool thin_fanout_fwd_pool_ok(const ghm_conv_desc* d, int act) {
+// (the pooled values leave as float2, the mask bytes in pairs: 8- and 2-byte aligned; null pointers pass)
+bool thin_fanout_fwd_pool_ok(const ghm_conv_desc* d, int act, const float* pooled, const unsigned char* mask) {
+    if ((uintptr_t)pooled % 8 != 0 || (uintptr_t)mask % 2 != 0) return false;
     if (!(thin_enabled() && fanout_act_ok(act) && d->K == 64 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W)) return false;
     const int q = d->C * d->kh * d->kw;
     const size_t lds = (size_t)(2 * 32 + 4 * 18 + 2 * d->C * (d->kh + 1) * ((((d->Wo - 1) + d->kw) + 63) & ~63)) * sizeof(float);
@@ -578,6 +588,8 @@ int thin_fanout_fwd_pool(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, c
                          float* pooled, unsigned char* mask, int act, float alpha, void* yq, long yq_nstride, int q_dt) {
     FanoutArgs a;
     memset(&a, 0, sizeof(a));
+    GHM_CHECK((uintptr_t)pooled % 8 == 0 && (uintptr_t)mask % 2 == 0,
+              "thin pooled forward: the pooled output must be 8-byte and the mask 2-byte aligned (no other kernel serves <= 4 channels)");
     GHM_CHECK(!yq || (((uintptr_t)yq & 15) == 0 && (q_dt == GHM_DTYPE_BF16 || q_dt == GHM_DTYPE_F16 || q_dt == 3 || q_dt == 4)),
               "thin pooled forward with a q output: 16-byte aligned q tensor, bf16 / f16");
     a.out_q = (uint2*)yq; a.out_q_nstride = yq_nstride; a.q_dt = q_dt;
@@ -613,10 +625,10 @@ int thin_fanout_fwd_pool(ghm_ctx* ctx, const ghm_conv_desc* d, const float* x, c
 }
 
 // data gradient (stride 1) of a conv with <= 4 filters: dx[C big] <- dy[K small]
-bool thin_fanout_dgrad_ok(const ghm_conv_desc* d, int act) {
+bool thin_fanout_dgrad_ok(const ghm_conv_desc* d, int act, const float* dx) {
     return thin_enabled() && fanout_act_ok(act) && d->stride == 1 && d->Ho == d->H && d->Wo == d->W &&
            (long)d->N * d->H * d->W >= 32768 && (long)d->K * d->Ho * d->Wo < (1L << 30) &&
-           fanout_geometry_ok(d->C, d->K, d->kh, d->kw, 1, d->H, d->W);
+           fanout_geometry_ok(d->C, d->K, d->kh, d->kw, 1, d->H, d->W) && fanout_out_aligned(d->C, dx, d->x_nstride);
 }
 
 int thin_fanout_dgrad(ghm_ctx* ctx, const ghm_conv_desc* d, const float* dy, const float* wp, const float* bias,
@@ -624,6 +636,7 @@ int thin_fanout_dgrad(ghm_ctx* ctx, const ghm_conv_desc* d, const float* dy, con
     FanoutArgs a;
     memset(&a, 0, sizeof(a));
     const int T = d->kh * d->kw;
+    GHM_CHECK(fanout_out_aligned(d->C, dx, d->x_nstride), "thin data gradient: output pointer / sample stride not aligned to its vector stores");
     a.in = dy; a.wp = wp; a.bias = bias; a.out = dx; a.zeros = ctx->zeros;
     a.N = d->N; a.CS = d->K; a.Hin = d->Ho; a.Win = d->Wo; a.in_nstride = d->y_nstride;
     a.R = d->C; a.Hout = d->H; a.Wout = d->W; a.out_nstride = d->x_nstride;

@@ -425,6 +425,8 @@ def view_layout(shape, view):
         ns, el0 = (C + WIDER) * hw, FRONT + 8 * hw
     elif view == 'offset':
         ns, el0 = chw, FRONT + OFFSET
+    elif view == 'off4':            # four bytes in: what a vector store cannot take (tests/conv_thin_ref.py's guard rows)
+        ns, el0 = chw, FRONT + 1
     else:
         assert view == 'whole'
         ns, el0 = chw, FRONT
