@@ -1292,6 +1292,27 @@ class Ops:
         call("ghm_route_parents", self.h, _vp(cost_ptr), int(c_pitch), int(H), int(W), _vp(parent_ptr), int(p_pitch),
              _vp(workspace_ptr))
 
+    # earthworks (csrc/earthworks.hip, gan_heightmaps_amd/earthworks.py)
+    @staticmethod
+    def earthworks_lds_bytes(reach):
+        """bytes of LDS a block of the tiled nearest-mark form uses for this reach, or -1 for a reach out of range"""
+        return int(_lib.load().ghm_earthworks_lds_bytes(int(reach)))
+
+    def earthworks_nearest(self, marks_ptr, m_pitch, H, W, threshold, reach, tiled, nearest_ptr, n_pitch, dist2_ptr, d_pitch):
+        """the nearest marked cell (marks >= threshold, a uint32 plane of H x W in rows of m_pitch cells) within ``reach`` of
+        every cell -> its flat index in the int32 plane at nearest_ptr and its squared distance in the one at dist2_ptr, -1 where
+        there is none; asynchronous"""
+        call("ghm_earthworks_nearest", self.h, _vp(marks_ptr), int(m_pitch), int(H), int(W), int(threshold), int(reach),
+             int(bool(tiled)), _vp(nearest_ptr), int(n_pitch), _vp(dist2_ptr), int(d_pitch))
+
+    def earthworks_shape(self, h_ptr, h_pitch, nearest_ptr, n_pitch, dist2_ptr, d_pitch, target_ptr, t_pitch, table_ptr, reach,
+                         mode, H, W, out_ptr, o_pitch):
+        """the fp32 heights at h_ptr blended towards target[nearest] by the (keep, take) pairs at table_ptr (reach^2 + 1 of
+        them, indexed by dist2) -> the fp32 plane at out_ptr; mode 0 both, 1 cut, 2 fill; asynchronous"""
+        call("ghm_earthworks_shape", self.h, _vp(h_ptr), int(h_pitch), _vp(nearest_ptr), int(n_pitch), _vp(dist2_ptr),
+             int(d_pitch), _vp(target_ptr), int(t_pitch), _vp(table_ptr), int(reach), int(mode), int(H), int(W), _vp(out_ptr),
+             int(o_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

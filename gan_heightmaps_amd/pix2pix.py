@@ -251,6 +251,42 @@ class Pix2Pix:
         self.engine.sync()
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, cost_field, paths, road, value_range=self.is_b_grayscale)
 
+    def carve_heightmap(self, heightmap, marks, target, profile, **kw):
+        """A heightmap shaped towards ``target`` around the marked cells, on the GPU (gan_heightmaps_amd/earthworks.py, DESIGN
+        §4v).  Not in the reference.  marks: an integer plane, marked where >= ``threshold``; target: a float plane read at the
+        marked cells alone; profile: an earthworks.Profile; kw: earthworks.carve's (threshold, tiled, keep, origin).  Returns an
+        earthworks.Earthworks with ``height`` and the volumes ``cut`` and ``fill``.  Leaves the training state untouched."""
+        from .earthworks import carve
+        from .step import LANE_OF
+        self.engine.sync()
+        return carve(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, marks, target, profile, **kw)
+
+    def cut_rivers(self, hydro, channel=None, **kw):
+        """River channels cut into the filled surface of ``hydro`` (heightmap_hydrology's).  Not in the reference.
+        channel: an earthworks.Channel (default Channel()); kw: earthworks.carve's (tiled, keep, origin).  Returns an
+        earthworks.Earthworks.  Intended use:
+
+            hydro = model.heightmap_hydrology(heightmap)
+            roads = model.heightmap_routes(hydro.filled, towns, hydro=hydro)
+            ground = model.cut_rivers(hydro).height
+            ground = model.grade_roads(ground, roads, roads.paths(villages)).height      # what Scene and heightmap_mesh take
+
+        Leaves the training state untouched."""
+        from .earthworks import cut_rivers
+        from .step import LANE_OF
+        self.engine.sync()
+        return cut_rivers(self.engine.ops[LANE_OF['dcgan_gen']], hydro, channel, **kw)
+
+    def grade_roads(self, heightmap, cost_field, paths=(), roadbed=None, traffic_threshold=None, **kw):
+        """Roadbeds graded into a heightmap of the field's size.  Not in the reference.  cost_field:
+        heightmap_routes'; paths: what its ``path`` / ``paths`` return; with ``traffic_threshold`` the cells that at least so
+        many cells travel through are graded instead.  roadbed: an earthworks.Roadbed (default Roadbed()); kw:
+        earthworks.carve's (tiled, keep, origin).  Returns an earthworks.Earthworks.  Leaves the training state untouched."""
+        from .earthworks import grade_roads
+        from .step import LANE_OF
+        self.engine.sync()
+        return grade_roads(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, cost_field, paths, roadbed, traffic_threshold, **kw)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

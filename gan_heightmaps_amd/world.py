@@ -33,9 +33,10 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
 
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
-        [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]]
+        [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT]
 """
 import argparse
+import collections
 import contextlib
 import os
 import re
@@ -57,8 +58,12 @@ from .util import is_int as _is_int, is_number as _is_number
 
 __all__ = ["HEAD_BLOCK", "MAX_BATCH", "SCENE_BYTES_PER_PIXEL", "SKY_SCENE_BYTES_PER_PIXEL", "world_latent", "axis_chunks", "axis_tiles", "seed_cells",
            "window_elements", "default_chunk_cells", "slot_batches", "erosion_sources", "snap_out", "plan_windows", "TerrainWorld",
+           "WorldEarthworks",
            "parse_region",
            "parse_args", "main"]
+
+# what TerrainWorld.earthworks returns: the carved ground, the hydrology and the travel field it came from, the graded paths
+WorldEarthworks = collections.namedtuple("WorldEarthworks", "height hydro cost_field paths")
 
 HEAD_BLOCK = 8                   # the head runs over world-aligned blocks of HEAD_BLOCK x HEAD_BLOCK cells, one pass each
 MAX_BATCH = 32                   # GHM_WORLD_MAX_TILES (include/ghm.h): tiles per forward pass
@@ -701,6 +706,32 @@ class TerrainWorld:
         hm = self._unit_height(y0, x0, h, w)
         return field(self._ops, hm, sources, origin=(y0, x0), **kw)
 
+    def earthworks(self, y0, x0, h, w, sources=None, targets=(), rivers=True, channel=None, roadbed=None, travel=None, tiled=None):
+        """the ground of ``self.heightmap(y0, x0, h, w)`` with its river channels cut and its roads graded (earthworks, DESIGN
+        §4v), heights mapped as a scene's; a plain or an eroded world.  The rectangle's hydrology is analysed
+        (``self.hydrology``) and, with rivers=True, the rivers are cut into its filled surface (channel: an
+        earthworks.Channel).  With ``sources`` -- (row, col) cells in world coordinates inside the rectangle -- the travel field
+        is computed on the filled surface with ``hydro=`` (travel: a route.Travel) and the paths from ``targets`` (world
+        coordinates too) are graded into the river-cut surface (roadbed: an earthworks.Roadbed).  tiled: the form of every
+        step.  Returns a WorldEarthworks record: ``height`` (float32 (h, w)), ``hydro``, ``cost_field`` (None without sources;
+        its origin is (y0, x0)) and ``paths`` (world coordinates).
+        Earthworks are a property of the rectangle, as its hydrology and its routes are: two rectangles do NOT agree where
+        they overlap.  Nothing is cached and no seam is handled."""
+        from . import earthworks as _ew
+        from .route import field
+        y0, x0 = int(y0), int(x0)
+        hydro = self.hydrology(y0, x0, h, w, tiled=tiled)
+        height = hydro.filled
+        if rivers:
+            height = _ew.cut_rivers(self._ops, hydro, channel, tiled=tiled, origin=(y0, x0)).height
+        cf, paths = None, []
+        if sources is not None:
+            cf = field(self._ops, hydro.filled, sources, travel, hydro=hydro, tiled=tiled, origin=(y0, x0))
+            paths = cf.paths(targets)
+            if paths:
+                height = _ew.grade_roads(self._ops, height, cf, paths, roadbed, tiled=tiled).height
+        return WorldEarthworks(height, hydro, cf, paths)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -887,6 +918,9 @@ def parse_args(argv):
                    help="a source of --routes, inside the region; repeat for more")
     p.add_argument("--to", dest="targets", type=parse_cell, action="append", metavar="Y,X", default=[],
                    help="a cell whose path to its source --routes writes; repeat for more")
+    p.add_argument("--earthworks", default=None, metavar="OUT",
+                   help="also write the region's ground with its river channels cut and, with --routes, the roads from the --to "
+                        "cells graded (earthworks' defaults): .npy (float32 (H, W)), or PNG")
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
@@ -962,6 +996,12 @@ def main(argv=None):
                 np.save("%s.%s.npy" % (a.routes, k), getattr(cf, k))
             for i, path in enumerate(cf.paths(a.targets)):
                 np.save("%s.path%d.npy" % (a.routes, i), path)
+        if a.earthworks:
+            ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
+            if a.earthworks.endswith(".npy"):
+                np.save(a.earthworks, ground)
+            else:
+                util.save_png(a.earthworks, util.to_uint8(ground))
     if a.output.endswith(".npy"):
         hm.flush()
     else:
