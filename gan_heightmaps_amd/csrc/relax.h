@@ -1,7 +1,7 @@
 // What the monotone relaxations share (hydrology.hip; route.hip): the one device word a block raises
 // when it changed a cell, the checks of a plane, and the host loop that issues sweeps in groups and reads that word once per
-// group.  The names are those of their first user.  Internal: included by those two files, and by earthworks.hip for
-// the checks of a plane, after common.h.
+// group.  The names are those of their first user.  Internal: included by those two files, by scatter.hip, whose
+// thinning is a relaxation of the same kind, and by earthworks.hip for the checks of a plane, after common.h.
 #pragma once
 #include "common.h"
 

@@ -1313,6 +1313,41 @@ class Ops:
              int(d_pitch), _vp(target_ptr), int(t_pitch), _vp(table_ptr), int(reach), int(mode), int(H), int(W), _vp(out_ptr),
              int(o_pitch))
 
+    # scatter (csrc/scatter.hip, gan_heightmaps_amd/scatter.py)
+    @staticmethod
+    def scatter_workspace(H, W):
+        """bytes of device workspace scatter_thin needs for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_scatter_workspace(int(H), int(W)))
+
+    @staticmethod
+    def scatter_lds_bytes(s2):
+        """bytes of LDS a block of the tiled thinning uses for this squared spacing, or -1 for an s2 out of range"""
+        return int(_lib.load().ghm_scatter_lds_bytes(int(s2)))
+
+    def scatter_chance(self, h_ptr, h_pitch, H, W, tables_ptr, height_scale, density, chance_ptr, c_pitch, dist2_ptr=None,
+                       d_pitch=0, water_ptr=None, water_n=0, blocked_ptr=None, b_pitch=0, threshold=1):
+        """the chance of every cell of the fp32 plane at h_ptr to be a candidate, in units of 2^-24 -> the uint32 plane at
+        chance_ptr; tables_ptr: the 384 fp32 of altitude weights, slope bounds and slope weights; dist2 (int32) with the
+        water_n + 1 fp32 weights at water_ptr, and blocked (uint32, >= threshold) are optional; asynchronous"""
+        call("ghm_scatter_chance", self.h, _vp(h_ptr), int(h_pitch), int(H), int(W), _vp(tables_ptr), float(height_scale),
+             float(density), _vp(dist2_ptr), int(d_pitch), _vp(water_ptr), int(water_n), _vp(blocked_ptr), int(b_pitch),
+             int(threshold), _vp(chance_ptr), int(c_pitch))
+
+    def scatter_candidates(self, chance_ptr, c_pitch, H, W, seed, origin, state_ptr, s_pitch, priority_ptr, p_pitch):
+        """the candidates (uint8: 1 or 0) and priorities (uint32) of the cells of a plane whose cell [0, 0] lies at the world
+        position ``origin`` = (row, col), hashed from the 64-bit seed and the world position; asynchronous"""
+        call("ghm_scatter_candidates", self.h, _vp(chance_ptr), int(c_pitch), int(H), int(W), int(seed) & ((1 << 64) - 1),
+             int(origin[0]), int(origin[1]), _vp(state_ptr), int(s_pitch), _vp(priority_ptr), int(p_pitch))
+
+    def scatter_thin(self, priority_ptr, p_pitch, state_ptr, s_pitch, H, W, s2, tiled, workspace_ptr):
+        """the Poisson-disk thinning of the candidates in the uint8 plane at state_ptr (1 -> 2 kept or 3 rejected), in place:
+        no two kept cells with dy^2 + dx^2 < s2, the greedy choice in (priority, row, col) order.  Returns the launches
+        issued; waits for the stream"""
+        sweeps = C.c_int64(0)
+        call("ghm_scatter_thin", self.h, _vp(priority_ptr), int(p_pitch), _vp(state_ptr), int(s_pitch), int(H), int(W), int(s2),
+             int(bool(tiled)), _vp(workspace_ptr), C.byref(sweeps))
+        return int(sweeps.value)
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

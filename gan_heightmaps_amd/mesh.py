@@ -148,10 +148,13 @@ class TerrainMesh:
         winding, positive in (col, row), looks down"""
         return np.ascontiguousarray(self.triangles[:, [0, 2, 1]])
 
-    def save(self, path, texture=None, height_scale=64.0):
+    def save(self, path, texture=None, height_scale=64.0, instances=None):
         """write the mesh: .glb (binary glTF 2.0: one mesh, POSITION with min / max, TEXCOORD_0, uint32 indices; the texture
         embedded as a PNG), .obj (with .mtl and the texture's .png beside it when a texture is given) or .npz (the arrays).
-        texture: uint8 (H, W, 3) or (H, W)."""
+        texture: uint8 (H, W, 3) or (H, W).  instances: a scatter.Scatter whose points lie in this mesh's frame (.glb only): one
+        more node per species, a four-sided cone as a proxy mesh, placed by EXT_mesh_gpu_instancing's TRANSLATION, ROTATION
+        and SCALE accessors in ``positions``' convention -- (col, height_scale h, row), the yaw about +y; without it the file
+        is byte for byte what it was before instances existed."""
         ext = os.path.splitext(path)[1].lower()
         if ext not in (".glb", ".obj", ".npz"):
             raise ValueError("a mesh is written as .glb, .obj or .npz, got %r" % (path,))
@@ -160,6 +163,8 @@ class TerrainMesh:
             if texture.dtype != np.uint8 or not (texture.ndim == 2 or (texture.ndim == 3 and texture.shape[2] == 3)):
                 raise ValueError("texture must be uint8 (H, W, 3) or (H, W), got %s %s" % (texture.dtype, texture.shape))
         _check_scale(height_scale)
+        if instances is not None and (ext != ".glb" or not hasattr(instances, "layers")):
+            raise ValueError("instances go into a .glb and are a scatter.Scatter, got %r for %r" % (instances, path))
         if ext == ".npz":
             extra = {} if texture is None else {"texture": texture}
             np.savez(path, grid=self.grid, heights=self.heights, triangles=self.triangles, shape=np.asarray(self.shape),
@@ -167,7 +172,7 @@ class TerrainMesh:
                      valid_shape=np.asarray(self.valid_shape), **extra)
         elif ext == ".glb":
             with open(path, "wb") as f:
-                f.write(_glb(self, texture, height_scale))
+                f.write(_glb(self, texture, height_scale, instances))
         else:
             _write_obj(self, path, texture, height_scale)
         return path
@@ -181,7 +186,7 @@ def _png_bytes(texture):
     return buf.getvalue()
 
 
-def _glb(mesh, texture, height_scale):
+def _glb(mesh, texture, height_scale, instances=None):
     pos, uv, idx = mesh.positions(height_scale), mesh.uvs(), mesh.front_faces()
     parts, views = [], []
 
@@ -212,6 +217,8 @@ def _glb(mesh, texture, height_scale):
         doc["textures"] = [{"source": 0, "sampler": 0}]
         doc["samplers"] = [{"magFilter": 9729, "minFilter": 9987, "wrapS": 33071, "wrapT": 33071}]
         doc["images"] = [{"bufferView": img, "mimeType": "image/png"}]
+    if instances is not None:
+        _glb_instances(doc, accessors, view, instances, height_scale)
     doc["bufferViews"] = views
     binary = b"".join(parts)
     doc["buffers"] = [{"byteLength": len(binary)}]
@@ -220,6 +227,42 @@ def _glb(mesh, texture, height_scale):
     total = 12 + 8 + len(text) + 8 + len(binary)
     return b"".join((struct.pack("<4sII", b"glTF", 2, total), struct.pack("<I4s", len(text), b"JSON"), text,
                      struct.pack("<I4s", len(binary), b"BIN\0"), binary))
+
+
+# the proxy of an instance: a cone of height 1 on a square base of side 1 around the origin, faces counter-clockwise from outside
+_CONE = (np.array([[-0.5, 0, -0.5], [0.5, 0, -0.5], [0.5, 0, 0.5], [-0.5, 0, 0.5], [0, 1, 0]], np.float32),
+         np.array([[0, 4, 1], [1, 4, 2], [2, 4, 3], [3, 4, 0], [0, 1, 2], [0, 2, 3]], np.uint16))
+
+
+def _glb_instances(doc, accessors, view, instances, height_scale):
+    """one node per layer of the Scatter: the cone, instanced by EXT_mesh_gpu_instancing"""
+    hs = np.float32(height_scale)
+    cone, faces = _CONE
+    accessors.append({"bufferView": view(cone.tobytes(), 34962), "componentType": 5126, "count": len(cone), "type": "VEC3",
+                      "min": [-0.5, 0.0, -0.5], "max": [0.5, 1.0, 0.5]})
+    accessors.append({"bufferView": view(faces.tobytes(), 34963), "componentType": 5123, "count": int(faces.size), "type": "SCALAR"})
+    doc["meshes"].append({"primitives": [{"attributes": {"POSITION": len(accessors) - 2}, "indices": len(accessors) - 1,
+                                          "mode": 4}], "name": "cone"})
+    doc["extensionsUsed"] = ["EXT_mesh_gpu_instancing"]
+    for layer in instances.layers:
+        n = len(layer)
+        if n == 0:                      # an accessor holds at least one element: a species without points gets no node
+            continue
+        tr = np.empty((n, 3), np.float32)
+        tr[:, 0] = layer.points[:, 1].astype(np.float32)
+        tr[:, 1] = hs * layer.height
+        tr[:, 2] = layer.points[:, 0].astype(np.float32)
+        half = layer.yaw.astype(np.float64) / 2
+        rot = np.zeros((n, 4), np.float32)
+        rot[:, 1], rot[:, 3] = np.sin(half), np.cos(half)
+        sc = np.repeat(layer.scale.astype(np.float32)[:, None], 3, axis=1)
+        attrs = {}
+        for key, data, kind in (("TRANSLATION", tr, "VEC3"), ("ROTATION", rot, "VEC4"), ("SCALE", sc, "VEC3")):
+            accessors.append({"bufferView": view(np.ascontiguousarray(data).tobytes()), "componentType": 5126, "count": n,
+                              "type": kind})
+            attrs[key] = len(accessors) - 1
+        doc["nodes"].append({"mesh": 1, "name": layer.species.name, "extensions": {"EXT_mesh_gpu_instancing": {"attributes": attrs}}})
+        doc["scenes"][0]["nodes"].append(len(doc["nodes"]) - 1)
 
 
 def _write_obj(mesh, path, texture, height_scale):

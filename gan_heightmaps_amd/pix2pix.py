@@ -287,6 +287,35 @@ class Pix2Pix:
         self.engine.sync()
         return grade_roads(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, cost_field, paths, roadbed, traffic_threshold, **kw)
 
+    def scatter_heightmap(self, heightmap, species, **kw):
+        """Trees and rocks placed on a heightmap by Poisson-disk sampling, on the GPU (gan_heightmaps_amd/scatter.py, DESIGN
+        §4w).  Not in the reference.  species: a scatter.Species or a list of them; kw: scatter.scatter's (seed, origin, hydro,
+        roads, blocked, height_scale, tiled, keep).  Returns a scatter.Scatter: per species the points, their heights, yaws
+        and scales.  Intended use:
+
+            hydro = model.heightmap_hydrology(heightmap)
+            forest = model.scatter_heightmap(hydro.filled, [scatter.Species("rock", 9.0), scatter.Species("pine", 4.0,
+                                             seed_stream=1)], hydro=hydro)            # the wider spacing first
+            painted = model.paint_scatter(texture, forest, [(0.5, 0.5, 0.5), (0.1, 0.3, 0.1)])
+            model.heightmap_mesh(hydro.filled, max_error).save("land.glb", texture=painted, instances=forest)
+
+        Leaves the training state untouched."""
+        from .scatter import scatter
+        from .step import LANE_OF
+        self.engine.sync()
+        return scatter(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, species, **kw)
+
+    def paint_scatter(self, texture, scatter, colours=(0.10, 0.28, 0.12), radius=1, opacity=0.9):
+        """A texture (this model's generators' or the uint8 paths', of the scatter's size) with the points of a scatter.Scatter
+        painted on it, layer after layer, by the hydrology's paint kernel.  Not in the reference.  colours: three
+        numbers in [0, 1] or one such triple per species; radius: pixels around a point, 0 .. 4.  Unpainted pixels keep their
+        bits.  Leaves the training state untouched."""
+        from .scatter import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, scatter, colours, radius, opacity,
+                     value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

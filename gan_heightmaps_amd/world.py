@@ -33,7 +33,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
 
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
-        [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT]
+        [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT] [--scatter OUT --spacing X]
 """
 import argparse
 import collections
@@ -732,6 +732,28 @@ class TerrainWorld:
                 height = _ew.grade_roads(self._ops, height, cf, paths, roadbed, tiled=tiled).height
         return WorldEarthworks(height, hydro, cf, paths)
 
+    def scatter(self, y0, x0, h, w, species, hydrology=False, roads=None, seed=None, **kw):
+        """trees and rocks placed on ``self.heightmap(y0, x0, h, w)`` (scatter.Scatter), heights mapped as a
+        scene's; a plain or an eroded world.  species: a scatter.Species or a list of them; the points come in world
+        coordinates (the Scatter's ``origin`` is (y0, x0)).  hydrology=True analyses the rectangle first (``self.hydrology``),
+        places on its filled surface and keeps the habitats' clearances from its lakes and rivers; roads: an integer or
+        boolean plane (h, w), non-zero on road cells -- ``route.raster(shape, paths, (y0, x0))`` of a field's paths, or its
+        traffic against a threshold.  seed: the draws' seed, default the world's.  kw: scatter.scatter's (blocked,
+        height_scale, tiled, keep).
+        Candidates and priorities are functions of the seed and the world position, and the chance without hydrology and
+        roads is one of the heights around a cell: two rectangles agree on them where they overlap (one cell inside the
+        edge, where the slope sees the neighbour).  The thinned set is NOT: like drainage and routes it belongs to the
+        rectangle, whose edge ends the search for conflicts, and with hydrology=True the wet ground is the rectangle's too.
+        Nothing is cached and no seam is handled."""
+        from .scatter import scatter
+        y0, x0 = int(y0), int(x0)
+        seed = self.seed if seed is None else seed
+        if hydrology:
+            hydro = self.hydrology(y0, x0, h, w, tiled=kw.get('tiled'), keep=('filled', 'depth', 'accumulation'))
+            return scatter(self._ops, hydro.filled, species, seed=seed, origin=(y0, x0), hydro=hydro, roads=roads, **kw)
+        hm = self._unit_height(y0, x0, h, w)
+        return scatter(self._ops, hm, species, seed=seed, origin=(y0, x0), roads=roads, **kw)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -921,6 +943,10 @@ def parse_args(argv):
     p.add_argument("--earthworks", default=None, metavar="OUT",
                    help="also write the region's ground with its river channels cut and, with --routes, the roads from the --to "
                         "cells graded (earthworks' defaults): .npy (float32 (H, W)), or PNG")
+    p.add_argument("--scatter", default=None, metavar="OUT",
+                   help="also write the points of one species placed on the region by Poisson-disk sampling (scatter's "
+                        "defaults, the world's seed): .npz or .csv; needs --spacing")
+    p.add_argument("--spacing", type=float, default=None, metavar="X", help="the spacing of --scatter, in cells (0 < X <= 32)")
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
@@ -937,6 +963,16 @@ def parse_args(argv):
         for y, x in a.sources + a.targets:
             if not (y0 <= y < y0 + h and x0 <= x < x0 + w):
                 p.error("the cell %d,%d lies outside the region %s" % (y, x, (a.region,)))
+    if (a.scatter is None) != (a.spacing is None):
+        p.error("--scatter and --spacing go together")
+    if a.scatter is not None:
+        if not (a.scatter.endswith(".npz") or a.scatter.endswith(".csv")):
+            p.error("--scatter writes .npz or .csv")
+        from .scatter import Species
+        try:
+            a.species = Species("tree", a.spacing)
+        except ValueError as e:
+            p.error(str(e))
     if a.chunk_cells is not None and a.chunk_cells < 1:
         p.error("--chunk-cells must be >= 1")
     if not 1 <= a.batch_size <= MAX_BATCH:
@@ -996,6 +1032,8 @@ def main(argv=None):
                 np.save("%s.%s.npy" % (a.routes, k), getattr(cf, k))
             for i, path in enumerate(cf.paths(a.targets)):
                 np.save("%s.path%d.npy" % (a.routes, i), path)
+        if a.scatter:
+            world.scatter(y0, x0, h, w, a.species).save(a.scatter)
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
