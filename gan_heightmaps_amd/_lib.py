@@ -99,6 +99,7 @@ SIGNATURES = {
     "ghm_conv2d_dgrad_lp_q": [_p, _D, _p, _i64, _p, _p, _p, _p, _i64, _i32, _f, _i32, _i32],
     "ghm_conv2d_dgrad_dact_lp_q": [_p, _D, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i32, _f, _i32],
     "ghm_lp_variant": [_D, _i32, _i32, C.c_char_p, _i32],
+    "ghm_sm_plan_query": [_D, _i32, _i32, C.POINTER(_i32 * 12)],
     "ghm_conv2d_bn_fwd": [_p, _D, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _f, _f, _i32, _f],
     "ghm_conv2d_bn_fwd_lp_q": [_p, _D, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _f, _f, _i32, _f, _i32],
     "ghm_bn_apply_q": [_p, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _f, _p, _i64, _i32],

@@ -59,6 +59,7 @@ struct Sm<GHM_DTYPE_F16> {
 
 constexpr int SM_MT = 128;          // pixels per block (4 waves x one 32-pixel MFMA column tile)
 constexpr int SM_MAXTAPS = 36;
+constexpr long SM_MAX_LDS = 160 * 1024;     // the ring's dynamic LDS limit (a CU's whole LDS)
 
 struct SmArgs {
     const u32x4* in_q;      // the operand q tensor: conv input (forward) / output gradient (data gradient)
@@ -554,6 +555,9 @@ SmPlan sm_plan(const ghm_conv_desc* d, int kind, int num_cu) {
     p.partial_bytes = (size_t)a.splits * a.R * Mtot * sizeof(float);
     long budget = 32 * 1024;       // (in-step, bf16, img/s: 32 KB 649.7, 64 KB 645.4, 144 KB 642.7 -- within the run-to-run spread; the small footprint is the principled choice)
     if (const char* f = GHM_OPT("GHM_SM_LDS_KB")) budget = atol(f) * 1024;
+    // the budget is a wish for ring DEPTH, not a geometry condition: a wish above the CU's LDS gets the deepest ring that fits
+    // (three slots, the minimum, fit for every variant: 144 KB for (25, 5)), so no plan asks for more than sm_launch_gemm allows
+    if (budget > SM_MAX_LDS) budget = SM_MAX_LDS;
 #define GHM_SM_RING(T_, Q_) \
     if (p.ntaps == T_ && p.nq == Q_) sm_ring_choice<T_, Q_>(p, budget, a.slabs_per_split);
     GHM_SM_RING(4, 1) GHM_SM_RING(4, 2) GHM_SM_RING(4, 5) GHM_SM_RING(9, 1) GHM_SM_RING(9, 2) GHM_SM_RING(9, 5)
@@ -567,7 +571,7 @@ template <int DT, int NTAPS, int NQ>
 int sm_launch_gemm(ghm_ctx* ctx, const SmPlan& p) {
     static bool attr_done = false;
     if (!attr_done) {
-        GHM_HIP(hipFuncSetAttribute((const void*)sm_gemm_kernel<DT, NTAPS, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        GHM_HIP(hipFuncSetAttribute((const void*)sm_gemm_kernel<DT, NTAPS, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM_MAX_LDS));
         attr_done = true;
     }
     hipLaunchKernelGGL((sm_gemm_kernel<DT, NTAPS, NQ>), p.grid, dim3(256), p.lds, ctx->stream, p.a);
@@ -617,8 +621,11 @@ bool sm_use(const ghm_conv_desc* d, int kind, int dtype) {
 int sm_conv(ghm_ctx* ctx, const ghm_conv_desc* d, int kind, const void* inq, long inq_ns, const float* in32, const void* wq,
             const float* bias, float* out32, long out_nstride, void* outq, long outq_ns, int act, float alpha, int accumulate,
             int dtype, const SmBn* bn) {
-    SmPlan p = sm_plan(d, kind, ctx->num_cu);
+    // planned with the CU count of the host-only queries (sm_use, ghm_sm_plan_query), not ctx->num_cu: the split count -- and
+    // with it the summation order -- is then the one the queries report on any device (the two are equal on the MI355X)
+    SmPlan p = sm_plan(d, kind, ghm_plan_cus());
     GHM_CHECK(p.ok, "sm_conv: geometry not served");
+    GHM_CHECK((long)p.lds <= SM_MAX_LDS, "sm_conv: the ring asks for %zu bytes of LDS", p.lds);
     GHM_CHECK(!(accumulate && (act != GHM_ACT_LINEAR || bn)), "sm_conv: accumulate needs a linear epilogue");
     GHM_CHECK(!(accumulate && !out32), "sm_conv: accumulate needs the fp32 output");
     GHM_CHECK(out32 || (outq && !bn), "sm_conv: no output");
@@ -695,6 +702,26 @@ int ghm_lp_variant(const ghm_conv_desc* d, int32_t kind, int32_t dtype, char* ou
     }
     const char* fam = kind == 2 ? "wgrad" : ((kind == 1 && d->stride == 2) ? "dgrad_s2" : "conv");
     snprintf(out, out_len, "lp_%s_kernel<%s, %d, %d>", fam, dt, d->kh, d->stride);
+    return 0;
+}
+
+// the plan of small-map product ``kind`` (0 forward, 1 data gradient) under the current tuning switches, as sm_conv would
+// launch it (planned with ghm_plan_cus(); nothing is launched, no context needed): out[0] served (the rest is zero when
+// not), [1] parity classes (1 / 4), [2] NTAPS and [3] NQ of the sm_gemm_kernel instantiation, [4] images per block, [5] walked
+// rows per block, [6] splits, [7] slabs per split, [8] ring slots, [9] ring LDS bytes, [10] the form of the finishing kernel
+// a BatchNorm rides in (256 / 1024 threads; 0: more than 1024 pixels per channel, no BatchNorm form), [11] the tap counts of
+// the classes, one byte each from class 0
+int ghm_sm_plan_query(const ghm_conv_desc* d, int32_t kind, int32_t dtype, int32_t* out) {
+    GHM_CHECK(d && out, "ghm_sm_plan_query: null argument");
+    memset(out, 0, 12 * sizeof(int32_t));
+    if (!sm_use(d, kind, dtype)) return 0;
+    const SmPlan p = sm_plan(d, kind, ghm_plan_cus());
+    const SmArgs& a = p.a;
+    const long Mtot = (long)a.N * a.OH * a.OW;
+    out[0] = 1; out[1] = a.ncls; out[2] = p.ntaps; out[3] = p.nq; out[4] = a.nimg; out[5] = a.rows;
+    out[6] = a.splits; out[7] = a.slabs_per_split; out[8] = a.pfs; out[9] = (int32_t)p.lds;
+    out[10] = Mtot <= 256 ? 256 : (Mtot <= 1024 ? 1024 : 0);
+    for (int c = 0; c < a.ncls; ++c) out[11] |= (a.cls_begin[c + 1] - a.cls_begin[c]) << (8 * c);
     return 0;
 }
 
