@@ -1348,6 +1348,48 @@ class Ops:
              int(bool(tiled)), _vp(workspace_ptr), C.byref(sweeps))
         return int(sweeps.value)
 
+    # viewshed (csrc/viewshed.hip, gan_heightmaps_amd/viewshed.py)
+    @staticmethod
+    def viewshed_top_elems(H, W):
+        """elements of the int32 plane of block maxima for a plane of H x W, or -1 for a size out of range"""
+        return int(_lib.load().ghm_viewshed_top_elems(int(H), int(W)))
+
+    def viewshed_quantise(self, h_ptr, h_pitch, H, W, height_scale, zq_ptr, z_pitch):
+        """the fp32 heights at h_ptr (finite, in [0, 1]) -> the int32 plane at zq_ptr, rint(h float32(height_scale 256)), in
+        1/256 cell; asynchronous"""
+        call("ghm_viewshed_quantise", self.h, _vp(h_ptr), int(h_pitch), int(H), int(W), float(height_scale), _vp(zq_ptr),
+             int(z_pitch))
+
+    def viewshed_top(self, zq_ptr, z_pitch, H, W, top_ptr, top_elems):
+        """the largest zq of every block of 16 x 16 cells -> the int32 [ceil(H / 16), ceil(W / 16)] at top_ptr; asynchronous"""
+        call("ghm_viewshed_top", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), _vp(top_ptr), int(top_elems))
+
+    @staticmethod
+    def _viewshed_table(observers):
+        obs = np.ascontiguousarray(observers, np.int64)
+        if obs.ndim != 2 or obs.shape[1] != 4:
+            raise ValueError("viewshed: the observers are an integer table [n, 4] of (row, col, eye_q, radius2), got %s" % (obs.shape,))
+        if obs.size and (obs.min() < -(1 << 31) or obs.max() >= 1 << 31):
+            raise ValueError("viewshed: an observer's field does not fit 32 bits")
+        obs = obs.astype(np.int32)
+        return obs, (obs.ctypes.data_as(C.POINTER(C.c_int32)) if obs.size else None)
+
+    def viewshed_sight(self, zq_ptr, z_pitch, H, W, observers, target_q, accel, top_ptr, count_ptr, c_pitch, mask_ptr=None,
+                       m_pitch=0):
+        """the number of ``observers`` -- a host table [n, 4] of (row, col, eye_q, radius2) -- that see each cell of the int32
+        plane at zq_ptr -> the uint32 plane at count_ptr, and bit i for observer i -> the one at mask_ptr (optional, n <= 32);
+        accel: jump runs of steps the block maxima at top_ptr prove clear (the same bits); asynchronous"""
+        obs, ptr = self._viewshed_table(observers)
+        call("ghm_viewshed_sight", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(obs.shape[0]), int(target_q),
+             int(bool(accel)), _vp(top_ptr), _vp(count_ptr), int(c_pitch), _vp(mask_ptr), int(m_pitch))
+
+    def viewshed_steps(self, zq_ptr, z_pitch, H, W, observers, target_q, accel, top_ptr, steps_ptr, s_pitch):
+        """viewshed_sight's launches with the steps tested per cell, over all observers -> the uint32 plane at steps_ptr (a
+        measuring aid); asynchronous"""
+        obs, ptr = self._viewshed_table(observers)
+        call("ghm_viewshed_steps", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(obs.shape[0]), int(target_q),
+             int(bool(accel)), _vp(top_ptr), _vp(steps_ptr), int(s_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

@@ -316,6 +316,34 @@ class Pix2Pix:
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, scatter, colours, radius, opacity,
                      value_range=self.is_b_grayscale)
 
+    def heightmap_viewshed(self, heightmap, observers, sight=None, accel=None):
+        """What a set of observers can see of a heightmap, by exact lines of sight on the GPU (gan_heightmaps_amd/viewshed.py,
+        DESIGN §4x).  Not in the reference.  observers: (row, col), (row, col, eye_height) or (row, col, eye_height, max_dist)
+        each; sight: a viewshed.Sight (default Sight()); accel: the form, the same bits either way.  Returns a
+        viewshed.Viewshed with ``count`` and ``mask``.  Intended use:
+
+            seen = model.heightmap_viewshed(heightmap, towers)
+            roads = model.heightmap_routes(heightmap, towns, penalty=seen.count.astype(np.float32))      # roads out of sight
+            forest = model.scatter_heightmap(heightmap, species, blocked=seen.visible(0))                # a clearing to look over
+            painted = model.paint_viewshed(texture, seen, hidden=True)
+
+        Leaves the training state untouched."""
+        from .viewshed import viewshed
+        from .step import LANE_OF
+        self.engine.sync()
+        return viewshed(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, observers, sight, accel)
+
+    def paint_viewshed(self, texture, viewshed, colour=(1.0, 0.85, 0.2), opacity=0.5, hidden=False):
+        """A texture (this model's generators' or the uint8 paths', of the viewshed's size) with the ground the observers of a
+        viewshed.Viewshed see -- hidden=True: the ground none of them sees -- blended towards ``colour`` by the hydrology's
+        paint kernel.  Not in the reference.  Unpainted pixels keep their bits.  Leaves the training state
+        untouched."""
+        from .viewshed import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, viewshed, colour, opacity, hidden,
+                     value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

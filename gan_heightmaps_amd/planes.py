@@ -34,7 +34,8 @@ def as_plane(heightmap, *, lead=True, unit_range=False, raw=False, what=None):
         skylight    False  False       False  None
         mesh        True   True        False  None
         hydrology   True   False       True   None            (route takes the hydrology's)
-        earthworks  True   False       True   None
+        earthworks  True   False       True   None            (scatter takes the same)
+        viewshed    True   True        True   None
     """
     a = heightmap if hasattr(heightmap, "dtype") and hasattr(heightmap, "shape") else np.asarray(heightmap)
     shape = tuple(a.shape)

@@ -34,6 +34,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
     python -m gan_heightmaps_amd.world EXPERIMENT MODEL OUT --seed N --region Y0,X0,H,W [--chunk-cells C]
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
         [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT] [--scatter OUT --spacing X]
+        [--viewshed OUT --from Y,X [--from Y,X ...]]
 """
 import argparse
 import collections
@@ -754,6 +755,19 @@ class TerrainWorld:
         hm = self._unit_height(y0, x0, h, w)
         return scatter(self._ops, hm, species, seed=seed, origin=(y0, x0), roads=roads, **kw)
 
+    def viewshed(self, y0, x0, h, w, observers, sight=None, accel=None):
+        """what ``observers`` see of ``self.heightmap(y0, x0, h, w)`` (viewshed.Viewshed), heights mapped as a
+        scene's; a plain or an eroded world.  observers: (row, col), (row, col, eye_height) or (row, col, eye_height, max_dist)
+        each, in world coordinates and inside the rectangle; the Viewshed's ``origin`` is (y0, x0) and its ``observers`` are in
+        world coordinates.  sight: a viewshed.Sight; accel: the form.
+        A sight line reads only the cells between its two ends, so visibility is a property of the world, not of the
+        rectangle: unlike hydrology, routes, earthworks and scatter, two rectangles that both hold the observers agree bit
+        for bit where they overlap, on ``count`` and on ``mask``.  Nothing is cached."""
+        from .viewshed import viewshed
+        y0, x0 = int(y0), int(x0)
+        hm = self._unit_height(y0, x0, h, w)
+        return viewshed(self._ops, hm, observers, sight, accel, origin=(y0, x0))
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -947,22 +961,30 @@ def parse_args(argv):
                    help="also write the points of one species placed on the region by Poisson-disk sampling (scatter's "
                         "defaults, the world's seed): .npz or .csv; needs --spacing")
     p.add_argument("--spacing", type=float, default=None, metavar="X", help="the spacing of --scatter, in cells (0 < X <= 32)")
+    p.add_argument("--viewshed", default=None, metavar="OUT",
+                   help="also write what observers at the --from cells (world coordinates) see of the region (viewshed's "
+                        "defaults): .npz (count, mask, observers) or .png (255 where seen)")
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
         if argv[i] in ("--region", "--from", "--to") and re.match(r"\s*-\d", argv[i + 1]):
             argv[i:i + 2] = [argv[i] + "=" + argv[i + 1]]
     a = p.parse_args(argv)
-    if a.routes is None:
-        if a.sources or a.targets:
-            p.error("--from / --to need --routes")
-    else:
+    if a.routes is None and (a.targets or (a.sources and a.viewshed is None)):
+        p.error("--from / --to need --routes (--from alone: or --viewshed)")
+    if a.routes is not None or a.viewshed is not None:
         if not a.sources:
-            p.error("--routes needs at least one --from Y,X")
+            p.error("--routes and --viewshed need at least one --from Y,X")
         y0, x0, h, w = a.region
         for y, x in a.sources + a.targets:
             if not (y0 <= y < y0 + h and x0 <= x < x0 + w):
                 p.error("the cell %d,%d lies outside the region %s" % (y, x, (a.region,)))
+    if a.viewshed is not None:
+        from .viewshed import MAX_OBSERVERS
+        if not (a.viewshed.endswith(".npz") or a.viewshed.lower().endswith(".png")):
+            p.error("--viewshed writes .npz or .png")
+        if len(a.sources) > MAX_OBSERVERS:
+            p.error("--viewshed takes at most %d --from cells" % MAX_OBSERVERS)
     if (a.scatter is None) != (a.spacing is None):
         p.error("--scatter and --spacing go together")
     if a.scatter is not None:
@@ -1034,6 +1056,8 @@ def main(argv=None):
                 np.save("%s.path%d.npy" % (a.routes, i), path)
         if a.scatter:
             world.scatter(y0, x0, h, w, a.species).save(a.scatter)
+        if a.viewshed:
+            world.viewshed(y0, x0, h, w, a.sources).save(a.viewshed)
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
