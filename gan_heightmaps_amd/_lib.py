@@ -214,6 +214,11 @@ SIGNATURES = {
     "ghm_viewshed_top": [_p, _p, _i32, _i32, _i32, _p, _i64],
     "ghm_viewshed_sight": [_p, _p, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _p, _p, _i32, _p, _i32],
     "ghm_viewshed_steps": [_p, _p, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _p, _p, _i32],
+    "ghm_contour_count": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, C.POINTER(_i64)],
+    "ghm_contour_trace": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, C.POINTER(_i64), C.POINTER(_i64),
+                          C.POINTER(_i32)],
+    "ghm_contour_extract": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "ghm_contour_marks": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -271,6 +276,8 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_scatter_workspace": ([_i32, _i32], C.c_int64),
             "ghm_scatter_lds_bytes": ([_i32], C.c_int64),
             "ghm_viewshed_top_elems": ([_i32, _i32], C.c_int64),
+            "ghm_contour_cells_bytes": ([_i32, _i32], C.c_int64),
+            "ghm_contour_workspace": ([_i32, _i32, _i64], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

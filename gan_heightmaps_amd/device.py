@@ -1390,6 +1390,48 @@ class Ops:
         call("ghm_viewshed_steps", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(obs.shape[0]), int(target_q),
              int(bool(accel)), _vp(top_ptr), _vp(steps_ptr), int(s_pitch))
 
+    # contours (csrc/contour.hip, gan_heightmaps_amd/contour.py)
+    @staticmethod
+    def contour_cells_bytes(H, W):
+        """bytes of the cells' buffer contour_count fills for a plane of H x W, or -1 for a size out of range"""
+        return int(_lib.load().ghm_contour_cells_bytes(int(H), int(W)))
+
+    @staticmethod
+    def contour_workspace(H, W, segments):
+        """bytes of device workspace contour_trace needs for a plane of H x W with this many segments, or -1"""
+        return int(_lib.load().ghm_contour_workspace(int(H), int(W), int(segments)))
+
+    def contour_count(self, zq_ptr, z_pitch, H, W, base_q, interval_q, count, cells_ptr):
+        """the contour segments of every cell of the int32 plane at zq_ptr for the levels 2 (base_q + j interval_q) + 1 (count:
+        -1 for every j, or the j in [0, count)) and their exclusive scan -> the buffer at cells_ptr.  Returns their number; waits
+        for the stream"""
+        segments = C.c_int64(0)
+        call("ghm_contour_count", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(base_q), int(interval_q), int(count),
+             _vp(cells_ptr), C.byref(segments))
+        return int(segments.value)
+
+    def contour_trace(self, zq_ptr, z_pitch, H, W, base_q, interval_q, count, cells_ptr, workspace_ptr, segments):
+        """links the segments contour_count counted and ranks them along their lines, in the workspace.  Returns (lines,
+        vertices, the ranking's doubling rounds); waits for the stream"""
+        lines, vertices, rounds = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        call("ghm_contour_trace", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(base_q), int(interval_q), int(count),
+             _vp(cells_ptr), _vp(workspace_ptr), int(segments), C.byref(lines), C.byref(vertices), C.byref(rounds))
+        return int(lines.value), int(vertices.value), int(rounds.value)
+
+    def contour_extract(self, zq_ptr, z_pitch, H, W, base_q, interval_q, count, cells_ptr, workspace_ptr, segments, lines, vertices,
+                        edge_ptr, t_ptr, offsets_ptr, level_ptr, closed_ptr):
+        """the traced lines -> edge int32 [V, 3], t float64 [V], offsets int64 [L + 1], level int32 [L], closed uint8 [L]; the
+        totals are contour_trace's; asynchronous once it has compared them with the workspace's"""
+        call("ghm_contour_extract", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(base_q), int(interval_q), int(count),
+             _vp(cells_ptr), _vp(workspace_ptr), int(segments), int(lines), int(vertices), _vp(edge_ptr), _vp(t_ptr),
+             _vp(offsets_ptr), _vp(level_ptr), _vp(closed_ptr))
+
+    def contour_marks(self, zq_ptr, z_pitch, H, W, base_q, interval_q, count, index_every, marks_ptr, m_pitch):
+        """0, 1 (a level between a cell and its right or lower neighbour) or 2 (an index contour: j % index_every == 0) -> the
+        uint32 plane at marks_ptr; asynchronous"""
+        call("ghm_contour_marks", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(base_q), int(interval_q), int(count),
+             int(index_every), _vp(marks_ptr), int(m_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

@@ -344,6 +344,34 @@ class Pix2Pix:
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, viewshed, colour, opacity, hidden,
                      value_range=self.is_b_grayscale)
 
+    def heightmap_contours(self, heightmap, levels=None, **kw):
+        """The contour lines of a heightmap as ordered polylines, traced on the GPU (gan_heightmaps_amd/contour.py).
+        Not in the reference.  levels: a contour.Levels (default Levels(): a line every 4 cells of height, every fifth an index
+        contour; count=1 is a single isoline at ``base``, a coastline); kw: contour.contours' (origin, max_segments, keep).
+        Returns a contour.Contours.  Intended use:
+
+            lines = model.heightmap_contours(heightmap)
+            lines.save("sheet.svg", texture=texture)                                  # or .geojson, .npz
+            coast = model.heightmap_contours(heightmap, Levels(base=sea_level, count=1))
+            painted = model.paint_contours(texture, heightmap)
+
+        Leaves the training state untouched."""
+        from .contour import contours
+        from .step import LANE_OF
+        self.engine.sync()
+        return contours(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, levels, **kw)
+
+    def paint_contours(self, texture, heightmap, levels=None, colour=(0.25, 0.15, 0.05), opacity=0.6, index_opacity=0.9):
+        """A texture (this model's generators' or the uint8 paths', of the heightmap's size) with the heightmap's contour lines
+        drawn on it, a pixel wide, the index contours heavier, by the hydrology's paint kernel.  heightmap: the
+        heightmap, or a contour.Contours that kept its 'zq'.  Not in the reference.  Unpainted pixels keep their bits.  Leaves
+        the training state untouched."""
+        from .contour import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, heightmap, levels, colour, opacity, index_opacity,
+                     value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -35,6 +35,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--blend mosaic|bilinear] [--dtype D] [--texture OUT_TEX [--overlap N] [--batch-size B]] [--erode N]
         [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT] [--scatter OUT --spacing X]
         [--viewshed OUT --from Y,X [--from Y,X ...]]
+        [--contours OUT.{svg,geojson,npz} [--interval X] [--base X] [--count N] [--index-every N]]
 """
 import argparse
 import collections
@@ -768,6 +769,20 @@ class TerrainWorld:
         hm = self._unit_height(y0, x0, h, w)
         return viewshed(self._ops, hm, observers, sight, accel, origin=(y0, x0))
 
+    def contours(self, y0, x0, h, w, levels=None):
+        """the contour lines of ``self.heightmap(y0, x0, h, w)`` (contour.Contours), heights mapped as a scene's; a
+        plain or an eroded world.  levels: a contour.Levels; the Contours' ``origin`` is (y0, x0) and its ``points`` are in world
+        coordinates.
+        A vertex reads the two cells at the ends of its grid edge and a segment the four corners of its cell, so the segments
+        are a property of the world, not of the rectangle: two rectangles' ``segments()`` agree bit for bit on every cell both
+        contain (``segments(within=...)`` keeps a rectangle's).  The lines themselves are NOT: they belong to the rectangle,
+        which cuts them at its edge, so where they start, how they are numbered and whether they close depends on it.
+        Nothing is cached."""
+        from .contour import contours
+        y0, x0 = int(y0), int(x0)
+        hm = self._unit_height(y0, x0, h, w)
+        return contours(self._ops, hm, levels, origin=(y0, x0))
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -964,10 +979,15 @@ def parse_args(argv):
     p.add_argument("--viewshed", default=None, metavar="OUT",
                    help="also write what observers at the --from cells (world coordinates) see of the region (viewshed's "
                         "defaults): .npz (count, mask, observers) or .png (255 where seen)")
+    p.add_argument("--contours", default=None, metavar="OUT",
+                   help="also write the region's contour lines in world coordinates (contour's height scale): .svg, .geojson or "
+                        ".npz; --interval, --base, --count and --index-every choose the levels")
+    from . import contour as _contour
+    _contour.add_level_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
-        if argv[i] in ("--region", "--from", "--to") and re.match(r"\s*-\d", argv[i + 1]):
+        if argv[i] in ("--region", "--from", "--to", "--base") and re.match(r"\s*-\d", argv[i + 1]):
             argv[i:i + 2] = [argv[i] + "=" + argv[i + 1]]
     a = p.parse_args(argv)
     if a.routes is None and (a.targets or (a.sources and a.viewshed is None)):
@@ -985,6 +1005,18 @@ def parse_args(argv):
             p.error("--viewshed writes .npz or .png")
         if len(a.sources) > MAX_OBSERVERS:
             p.error("--viewshed takes at most %d --from cells" % MAX_OBSERVERS)
+    chosen = (a.interval, a.base, a.count, a.index_every)
+    if a.contours is None:
+        d = _contour.Levels()
+        if chosen != (d.interval, d.base, d.count, d.index_every):
+            p.error("--interval / --base / --count / --index-every need --contours")
+    else:
+        if not a.contours.lower().endswith((".svg", ".geojson", ".npz")):
+            p.error("--contours writes .svg, .geojson or .npz")
+        try:
+            a.levels = _contour.Levels(*chosen)
+        except ValueError as e:
+            p.error(str(e))
     if (a.scatter is None) != (a.spacing is None):
         p.error("--scatter and --spacing go together")
     if a.scatter is not None:
@@ -1058,6 +1090,8 @@ def main(argv=None):
             world.scatter(y0, x0, h, w, a.species).save(a.scatter)
         if a.viewshed:
             world.viewshed(y0, x0, h, w, a.sources).save(a.viewshed)
+        if a.contours:
+            world.contours(y0, x0, h, w, a.levels).save(a.contours)
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
