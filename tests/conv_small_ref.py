@@ -30,7 +30,7 @@ import numpy as np
 
 from oracle import lp as LP
 from oracle import ops as O
-from tests.conv_s2_ref import FRONT, REL_L2, VIEWS, view_layout  # noqa: F401  (the views of tests/test_gpu_conv_s2.py's V / QV)
+from tests.conv_s2_ref import FRONT, REL_L2, VIEWS, view_layout  # noqa: F401  (the named views of tests/canary.py's View / QView)
 from tests.elementwise_q_ref import U, rel, worst  # noqa: F401  (re-exported for the two test modules)
 
 MODES = ('bf16', 'f16')

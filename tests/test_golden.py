@@ -108,7 +108,7 @@ def test_hip_step_matches_golden_trajectory(opt, lr):
     """3 consecutive train_fn calls from the seeded init, with NO resync to the oracle: losses within 1e-3 rel
     (north_star tolerance) of the float64 trajectory stored in tests/golden/step_*.npz"""
     from gan_heightmaps_amd import device as D
-    from tests.test_gpu_step import build_model
+    from tests.gpu_common import build_model
     want = np.load(os.path.join(G, "step_%s.npz" % opt))
     cfg = S.default_cfg(opt=opt, lr=lr, **SMALL)
     dev = D.Device(0)

@@ -36,63 +36,36 @@ test_bilinear_conv3_collapsed_onto_the_coarse_grid (tests/test_gpu_ops.py) still
 two added ones.
 Wall time on the MI355X: 46 tests in 3.6 s (2.9 s between the fixture's start and end), next to tests/test_gpu_conv_s2.py's 1.8 s.
 """
-import time
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import tuning_env
 from tests import blconv_frame_ref as R
+from tests import canary
 from tests import elementwise_q_ref as Q
-from tests.test_gpu_conv_s2 import Raw, V, clean, unchanged
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-COUNT = {}
 REACHED = set()
 _REF = {}
-_T0 = [None]
 CANARY32 = np.uint32(Q.CANARY * 0x10001)
+# (no second figure is asserted: the bound of a split product is per element; a bit-exact comparison of written values holds
+# their finiteness too)
+LEDGER = canary.Ledger(lambda kind, w, r, n: "measured %-6s worst k %6.3f of %2d  (%d comparisons)" % (kind, w, R.K_BOUND[kind], n),
+                       rel_limit=None, order=lambda m: [kind for kind in R.KINDS if kind in m])
+gpu, mem = canary.fixtures(LEDGER, _REF)
+cached = functools.partial(canary.cached, _REF)
+V, Raw = canary.View.named, canary.Bytes.rounded
+clean, unchanged, note, exact = canary.clean, canary.unchanged, LEDGER.note, LEDGER.exact
 
 
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.close()
-    _REF.clear()
-    for kind in R.KINDS:
-        if kind in MEASURED:
-            print("measured %-6s worst k %6.3f of %2d  (%d comparisons)" % (kind, MEASURED[kind], R.K_BOUND[kind], COUNT[kind]))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
-
-
-@pytest.fixture
-def mem(gpu):
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-class PV(V):
+class PV(canary.View):
     """a V of which only the pixels ``owned`` belong to the tensor: the others hold the canary pattern and count as outside"""
 
     def __init__(self, gpu, shape, view, data, owned):
-        super().__init__(gpu, shape, view)
+        super().__init__(gpu, shape, R.view_layout(shape, view))
         self.owned = np.ascontiguousarray(np.broadcast_to(owned, shape))
         bits = np.ascontiguousarray(data, np.float32).reshape(shape).view(np.uint32).copy()
         bits[~self.owned] = CANARY32
@@ -108,31 +81,6 @@ class PV(V):
         got = self.numpy()
         assert (got.view(np.uint32)[~self.owned] == CANARY32).all(), "a pixel the frame does not own was written"
         return got[self.owned]
-
-
-def exact(kind, got, want, what):
-    COUNT[kind] = COUNT.get(kind, 0) + 1
-    MEASURED.setdefault(kind, 0.0)
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape
-    assert np.isfinite(got).all(), (what, "%d written values are not finite" % (~np.isfinite(got)).sum())
-    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
-    if bad.size:
-        pytest.fail("%s %s: %d of %d elements differ in bits, first at flat border index %d: got %r, expected %r"
-                    % (kind, what, bad.size, got.size, bad[0], got[bad[0]], want[bad[0]]))
-
-
-def note(kind, g, splits, got, ref, M, what):
-    k = R.bound(kind, g, splits)
-    w = R.worst(got, ref, M)
-    print("%s %s: worst k %.3f (bound %d)" % (kind, what, w, k))
-    MEASURED[kind] = max(MEASURED.get(kind, 0.0), w)
-    COUNT[kind] = COUNT.get(kind, 0) + 1
-    assert np.isfinite(got).all(), (what, "%d written values are not finite" % (~np.isfinite(got)).sum())
-    if w > k:
-        err = np.where(got == ref, 0, np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300)))
-        i = int(np.argmax(err))
-        pytest.fail("%s %s: flat border index %d got %r ref %r: %.2f x 2^-24 M > k = %d" % (kind, what, i, got[i], ref[i], w, k))
 
 
 class Frame:
@@ -244,7 +192,7 @@ def test_reals(gpu, mem, row):
         prev = d['prev'][kind]
         assert (p != 0).all()                                               # no signed zero decides fl32(previous + increment)
         got = call(prev)
-        note(kind, row.g, splits[R.KINDS.index(kind)], got, r + p, m + np.abs(p.astype(np.float64)), "reals")
+        note(kind, got, r + p, m + np.abs(p.astype(np.float64)), "reals", k=R.bound(kind, row.g, splits[R.KINDS.index(kind)]))
         exact(kind, call(prev), got, "reals, repeated call")
         inc = call(np.zeros_like(prev))
         exact(kind, got, (p + inc).astype(np.float32), "reals, result == fl32(previous + increment)")

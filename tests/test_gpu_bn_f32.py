@@ -44,42 +44,25 @@ kernel ((2, 257, 64, 64), 8.4 MB, runs two blocks of it).  The mean-1000 channel
 conditioning term of inv is hundreds of ulp (tests/test_bn_f32_ref.py proves both).
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import call, tuning_env
 from tests import bn_f32_ref as R
+from tests import canary
 from tests import elementwise_q_ref as Q
-from tests.test_gpu_elementwise_f32 import gpu, mem  # noqa: F401  (the module-scoped device and the per-test clean-up)
-from tests.test_gpu_elementwise_f32 import V, clean, unchanged, note, exact, fl32_sum, MEASURED, COUNT
 
 pytestmark = pytest.mark.gpu
 
 A = R.ALPHA
 _REF = {}
-
-
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-def hold(op, got, ref, M, k, what):
-    """``note`` without the rel-L2 assertion, for comparisons whose reference may be (near) zero as a whole -- a channel that
-    cancels -- or lies an fp32 rounding of a large mean away: the per-element bound is the whole claim"""
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    w = R.worst(got, ref, M)
-    print("%s %s: worst k %.3f (bound %s)" % (op, what, w, k))
-    old = MEASURED.get(op, (0.0, 0.0))
-    MEASURED[op] = (max(old[0], w), old[1])
-    COUNT[op] = COUNT.get(op, 0) + 1
-    assert np.isfinite(got).all(), (op, what)
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s: element %s got %r ref %r: %.2f x 2^-24 M > k = %s" % (op, what, i, got[i], ref[i], w, k))
+LEDGER = canary.Ledger(lambda op, w, r, n: "measured %-22s worst k %7.3f  rel-L2 %.2e  (%d comparisons)" % (op, w, r, n))
+gpu, mem = canary.fixtures(LEDGER, _REF, loss_scale=True)
+cached = functools.partial(canary.cached, _REF)
+V, clean, unchanged, fl32_sum = canary.View.free, canary.clean, canary.unchanged, canary.fl32_sum
+note, exact = LEDGER.note, LEDGER.exact
 
 
 def vec(v):
@@ -109,11 +92,11 @@ def test_batchnorm(gpu, mem, row, why):
             ops.bn_stats(x.t, mean.t, inv.t, ws, rm.t, ri.t, R.EPS, R.RUN_ALPHA)
             m32, i32 = vec(mean), vec(inv)
             mu, var, iv = cached(('stats', shape, v), lambda: R.bn_stats(d['x']))
-            hold('bn_stats', m32, mu, np.abs(mu) + 1e-30, R.K_IN_STATS, tag + " mean")
-            note('bn_stats', i32, iv, R.inv_M(shape, mu, var, iv, L), R.K_IN_STATS, tag + " inv")
+            note('bn_stats', m32, mu, np.abs(mu) + 1e-30, tag + " mean", k=R.K_IN_STATS, rel_limit=False)
+            note('bn_stats', i32, iv, R.inv_M(shape, mu, var, iv, L), tag + " inv", k=R.K_IN_STATS)
             for t, s32, j in ((rm, m32, 0), (ri, i32, 1)):
                 ref, M = R.running(d['run'][j], s32)
-                hold('bn_running', vec(t), ref, M, R.K_RUN, tag + (" run_inv" if j else " run_mean"))
+                note('bn_running', vec(t), ref, M, tag + (" run_inv" if j else " run_mean"), k=R.K_RUN, rel_limit=False)
             if 'constant' in roles:
                 c = roles.index('constant')
                 assert m32[c] == np.float32(R.CONST) and i32[c] == np.float32(1 / np.sqrt(float(np.float32(R.EPS)))), tag
@@ -143,11 +126,11 @@ def test_batchnorm(gpu, mem, row, why):
                 kf = R.K_LIBM['in_fwd_tanh'] if act == 'tanh' else R.K_IN_FWD[act]
                 op = 'bn_forward/tanh' if act == 'tanh' else 'bn_forward'
                 if plain.any():
-                    note(op, y32[:, plain], yref[:, plain], M[:, plain], kf, what)
+                    note(op, y32[:, plain], yref[:, plain], M[:, plain], what, k=kf)
                 if not plain.all():         # the fp32 mean of the mean-1000 channel is 3e-5 off: M holds it, rel-L2 cannot
-                    hold(op, y32[:, ~plain], yref[:, ~plain], M[:, ~plain], kf, what + " mean-1000 channel")
+                    note(op, y32[:, ~plain], yref[:, ~plain], M[:, ~plain], what + " mean-1000 channel", k=kf, rel_limit=False)
                 y2ref, M2 = Q.bn_apply(d['x'], m32, i32, d['gamma'], d['beta'], act, A)
-                note('bn_apply/tanh' if act == 'tanh' else 'bn_apply', y32, y2ref, M2, Q.K_BN_APPLY[act], what + " from the stored mean / inv")
+                note('bn_apply/tanh' if act == 'tanh' else 'bn_apply', y32, y2ref, M2, what + " from the stored mean / inv", k=Q.K_BN_APPLY[act])
                 for c in range(C):          # variance 0: y = act(beta), whatever gamma
                     if one or roles[c] == 'constant':
                         want = Q.restate32_act(d['beta'][c:c + 1], act, A)[0] if act != 'tanh' else y32[0, c].flat[0]
@@ -164,10 +147,9 @@ def test_batchnorm(gpu, mem, row, why):
                 ops.bn_backward_x(dout.t, x.t, dx2.t, mean.t, inv.t, gamma.t, beta.t, dg3.t, db3.t, ws, act, A, accumulate=True)
                 ref, Mx, dgr, Mg, dbr, Mb = R.bn_backward(d['dout'], y32, d['x'], m32, i32, d['gamma'], act, A)
                 dx32, g32, b32 = dx.numpy(), vec(dg), vec(db)
-                note('bn_backward/tanh' if act == 'tanh' else 'bn_backward', dx32, ref, Mx,
-                     R.K_LIBM['in_bwd_tanh'] if act == 'tanh' else R.K_IN_BWD, what)
-                hold('bn_dgamma', g32, dgr, Mg, R.k_dgamma(act), what)
-                hold('bn_dbeta', b32, dbr, Mb, R.k_dgamma(act), what)
+                note('bn_backward/tanh' if act == 'tanh' else 'bn_backward', dx32, ref, Mx, what, k=R.K_LIBM['in_bwd_tanh'] if act == 'tanh' else R.K_IN_BWD)
+                note('bn_dgamma', g32, dgr, Mg, what, k=R.k_dgamma(act), rel_limit=False)
+                note('bn_dbeta', b32, dbr, Mb, what, k=R.k_dgamma(act), rel_limit=False)
                 if one:
                     assert not dx32.any(), (what, "one value per channel: dz - mean(dz) is exactly 0")
                 exact('bn_backward_x', dx2.numpy(), dx32, what + " dx == bn_backward's")
@@ -197,7 +179,7 @@ def test_channel_sum(gpu, mem, row, why):
         ref, M = R.channel_sum(d['x'])
         ops.channel_sum(x.t, out.t, False)
         inc = vec(out)
-        hold('channel_sum', inc, ref, M, R.k_channel_sum(shape, spec, False), what)
+        note('channel_sum', inc, ref, M, what, k=R.k_channel_sum(shape, spec, False), rel_limit=False)
         whole = np.array([R.CS_ROLES[(c + v) % 3] == 'integer' for c in range(C)])
         assert np.array_equal(inc[whole].astype(np.float64), ref[whole]), (what, "integer channels have an exact sum")
         clean(what, out)
@@ -205,7 +187,7 @@ def test_channel_sum(gpu, mem, row, why):
         ops.channel_sum(x.t, out.t, True)
         acc = vec(out)
         exact('channel_sum', acc, fl32_sum(d['prev'], inc), what + " accumulate")
-        hold('channel_sum', acc, ref + d['prev'], M + np.abs(d['prev']), R.k_channel_sum(shape, spec, True), what + " accumulate")
+        note('channel_sum', acc, ref + d['prev'], M + np.abs(d['prev']), what + " accumulate", k=R.k_channel_sum(shape, spec, True), rel_limit=False)
         assert np.array_equal(acc[whole].astype(np.float64), (ref + d['prev'])[whole]), (what, "integer channels, accumulated")
         clean(what, out)
         unchanged(what, x)
@@ -225,14 +207,14 @@ def test_scale_samples_rows(gpu, mem, row, why):
     got = x.numpy()
     ref, M = R.scale_samples(d['x'], d['num'], d['den'])
     live = d['den'] != 0
-    note('scale_samples', got[live], ref[live], M[live], R.K_SCALE, "%s (%s)" % (shape, why.split(":")[0]))
+    note('scale_samples', got[live], ref[live], M[live], "%s (%s)" % (shape, why.split(":")[0]), k=R.K_SCALE)
     if N >= 3:
         assert (got[N - 3] == 0).all(), (shape, "den == 0 behind exact zeros stays zero")
         nan = np.zeros(shape[1:], bool)
         nan[d['nan'][1:]] = True
         assert np.isnan(got[N - 2][nan]).all() and (got[N - 2][~nan] == 0).all(), (shape, "den == 0: NaN where x != 0, 0 elsewhere")
         assert (got[N - 1][d['x'][N - 1] != 0] != 0).all(), (shape, "a denormal den is no zero")
-        COUNT['scale_samples'] += 2
+        LEDGER.tally('scale_samples', 2)
     clean(shape, x)
     unchanged(shape, num, den)
 

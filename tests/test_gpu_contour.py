@@ -10,10 +10,7 @@ import pytest
 from oracle import step as ostep
 from gan_heightmaps_amd import contour as CT
 from tests import contour_ref as R
-from tests.test_gpu_hydrology import CANARY, Canvas, same
-from tests.test_gpu_route import padded
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, CANARY, Canvas, dev, model_params, ops, padded, same, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -174,7 +171,7 @@ def test_the_models_methods_and_the_paint(small_model, dev, ops):
 # ---- 3. the world: two rectangles agree on the cells both contain -------------------------------------------------------------------
 @pytest.mark.parametrize("eroded", (False, True))
 def test_two_rectangles_of_the_world_agree_bit_for_bit_on_their_common_cells(small_model, dev, ops, eroded):
-    from tests.test_gpu_erosion import ERO
+    from tests.gpu_common import ERO
     m = small_model
     kw = dict(erosion=ERO) if eroded else {}
     levels = CT.Levels(interval=1.0, index_every=4, height_scale=24.0)

@@ -38,208 +38,25 @@ the same zero for relu alone; and a failure message that did not format.  Wall t
 between the fixture's start and end).
 """
 import ctypes as C
-import time
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import load, tuning_env
+from tests import canary
 from tests import conv_s2_ref as R
 from tests import elementwise_q_ref as Q
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-COUNT = {}
 _REF = {}
-_T0 = [None]
-
-
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.close()
-    _REF.clear()
-    for key in sorted(MEASURED):
-        print("measured %-7s %-6s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)"
-              % (key + MEASURED[key][:1] + (R.K_BOUND[key],) + MEASURED[key][1:] + (COUNT[key],)))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
-
-
-@pytest.fixture
-def mem(gpu):
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-class V:
-    """an fp32 [N, C, H, W] view laid out by R.view_layout inside a canary-filled allocation"""
-
-    def __init__(self, gpu, shape, view, data=None):
-        self.dev, _, D = gpu
-        if len(shape) == 1:
-            shape = (1, shape[0], 1, 1)
-        N, C, H, W = shape
-        el0, ns, self.total = R.view_layout(shape, view)
-        self.ptr = self.dev.alloc(4 * self.total)
-        assert self.ptr % 16 == 0 and el0 >= R.FRONT and self.total - (el0 + (N - 1) * ns + C * H * W) >= R.FRONT
-        Q.canary_fill(self.dev, self.ptr, 4 * self.total)
-        self.t = D.DevTensor(self.dev, self.ptr + 4 * el0, shape, ns)
-        self.inside = Q.f32_inside(N, ns, el0, C * H * W, self.total)
-        self.data = None
-        if data is not None:
-            self.set(data)
-
-    def set(self, data):
-        self.data = np.ascontiguousarray(data, np.float32).reshape(self.t.shape).copy()
-        self.t.set(self.data)
-        return self
-
-    def numpy(self):
-        return self.t.numpy()
-
-    def stray(self):
-        return Q.canary_changed(self.dev, self.ptr, 4 * self.total, self.inside)
-
-    def same(self):
-        return Q.bits_equal(self.numpy(), self.data)
-
-
-class Raw:
-    """``nbytes`` of device memory (16-byte multiple) with 4 KB of canary in front and behind: packed weights, dW, workspaces"""
-
-    def __init__(self, gpu, nbytes, data=None):
-        self.dev, _, D = gpu
-        self.nbytes = (max(int(nbytes), 16) + 15) // 16 * 16
-        self.total = self.nbytes + 8 * R.FRONT
-        self.base = self.dev.alloc(self.total)
-        Q.canary_fill(self.dev, self.base, self.total)
-        self.ptr = self.base + 4 * R.FRONT
-        self.t = D.DevTensor(self.dev, self.ptr, (1, self.nbytes // 4, 1, 1))
-        self.inside = np.zeros(self.total // 2, bool)
-        self.inside[2 * R.FRONT:2 * R.FRONT + self.nbytes // 2] = True
-        self.data = None
-        if data is not None:
-            self.set(data)
-
-    def set(self, data):
-        self.data = np.ascontiguousarray(data, np.float32).ravel().copy()
-        assert self.data.nbytes == self.nbytes
-        self.dev.h2d(self.ptr, self.data)
-        return self
-
-    def numpy(self):
-        return self.t.numpy().ravel()
-
-    def snapshot(self):
-        self.data = self.numpy().copy()
-
-    def stray(self):
-        return Q.canary_changed(self.dev, self.base, self.total, self.inside)
-
-    def same(self):
-        return np.array_equal(self.numpy().view(np.uint32), self.data.view(np.uint32))
-
-
-class QV:
-    """a q tensor (whole, a channel slice [8, 8 + C) of C + 16 channels, or starting one unit further in) inside a canary-filled
-    allocation of PLANES[dtype] planes; the piece stride is that of the allocation (N * nstride), as the q outputs require"""
-    FRONT = 256                     # 16-byte units: 4 KB
-
-    def __init__(self, gpu, shape, dtype, view):
-        self.dev, _, D = gpu
-        N, C, H, W = shape
-        hw, self.planes = H * W, Q.PLANES[dtype]
-        wide = C + 16 if view == 'slice' else C
-        ns = wide // 8 * hw
-        front = self.FRONT + (1 if view == 'offset' else 0)
-        self.total_units = front + self.planes * N * ns + self.FRONT
-        self.ptr = self.dev.alloc(16 * self.total_units)
-        Q.canary_fill(self.dev, self.ptr, 16 * self.total_units)
-        base = D.QTensor(self.dev, self.ptr + 16 * front, (N, wide, H, W), dtype)
-        self.q = base.channels(8, 8 + C) if view == 'slice' else base
-        self.inside = Q.q_inside(self.planes, N, ns, N * ns, front + (hw if view == 'slice' else 0), C // 8 * hw, self.total_units)
-        self.data = None
-
-    def raw(self):
-        out = np.empty(8 * self.total_units, np.uint16)
-        self.dev.d2h(out, self.ptr, out.nbytes)
-        return out
-
-    def snapshot(self):
-        self.data = self.raw()
-
-    def stray(self):
-        return Q.canary_changed(self.dev, self.ptr, 16 * self.total_units, self.inside)
-
-    def same(self):
-        return np.array_equal(self.raw(), self.data)
-
-    def values(self):
-        """the stored pieces as float32 arrays"""
-        return tuple(self.q.numpy(p) for p in range(self.planes)) if self.planes > 1 else (self.q.numpy(),)
-
-
-def clean(what, *views):
-    for i, v in enumerate(views):
-        s = v.stray()
-        assert s.size == 0, (what, "buffer %d: %d halfwords outside it were written, first at halfword %d" % (i, s.size, s[0]))
-
-
-def unchanged(what, *views):
-    clean(what, *views)
-    for i, v in enumerate(views):
-        assert v.same(), (what, "input %d was modified" % i)
-
-
-def note(mode, kind, got, ref, M, what):
-    key = (mode, kind)
-    k = R.K_BOUND[key]
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    w, r = R.worst(got, ref, M), R.rel(got, ref)
-    print("%s %s %s: worst k %.3f (bound %d)  rel-L2 %.2e" % (mode, kind, what, w, k, r))
-    old = MEASURED.get(key, (0.0, 0.0))
-    MEASURED[key] = (max(old[0], w), max(old[1], r))
-    COUNT[key] = COUNT.get(key, 0) + 1
-    assert np.isfinite(got).all(), (what, "the output is not finite everywhere: %d elements" % (~np.isfinite(got)).sum())
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s %s: element %s (%s) got %r ref %r: %.2f x 2^-24 M > k = %d"
-                    % (mode, kind, what, i, R.parity_class(kind, i), got[i], ref[i], w, k))
-    assert r <= R.REL_L2[mode], (what, r)
-
-
-def exact(mode, kind, got, want, what, zero_sign=True):
-    """bit for bit; zero_sign False: a zero of either sign is a zero (relu: the epilogues that fold it into a piece-wise linear
-    slope return v * 0 = -0 for a negative v, the others max(v, 0) = +0)"""
-    key = (mode, kind)
-    COUNT[key] = COUNT.get(key, 0) + 1
-    MEASURED.setdefault(key, (0.0, 0.0))
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape
-    if not zero_sign:
-        got, want = np.where(got == 0, np.float32(0), got), np.where(want == 0, np.float32(0), want)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        i = tuple(bad[0])
-        pytest.fail("%s %s %s: %d of %d elements differ in bits, first at (n, channel, row, column) = %s (%s): got %r, expected %r"
-                    % (mode, kind, what, len(bad), got.size, i, R.parity_class(kind, i), got[i], want[i]))
+LEDGER = canary.Ledger(lambda key, w, r, n: "measured %-7s %-6s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)" % (key + (w, R.K_BOUND[key], r, n)),
+                       bound=R.K_BOUND.__getitem__, rel_limit=lambda key: R.REL_L2[key[0]], describe=lambda kind, i, shape: R.parity_class(kind, i))
+gpu, mem = canary.fixtures(LEDGER, _REF)
+cached = functools.partial(canary.cached, _REF)
+V, Raw, QV = canary.View.named, canary.Bytes.rounded, canary.QView.named
+clean, unchanged, note, exact = canary.clean, canary.unchanged, LEDGER.note, LEDGER.exact
 
 
 def act64(v, act):
@@ -356,7 +173,7 @@ class Product:
         unchanged(what, *self.inputs)
         clean(what, *(self.buffers + outs))
         for o in outs:
-            self.gpu[0].free(o.ptr if isinstance(o, V) else o.base)
+            self.gpu[0].free(o.base)
 
 
 def refs(mode, kind, g, d, key):
@@ -384,19 +201,19 @@ def test_row(gpu, mem, row):
         irb = iref if ib is None else iref + ib.astype(np.float64)[None, :, None, None]
         p = Product(gpu, mode, kind, g, row.view, di)
         outs = [p.out()]
-        exact(mode, kind, p.call(outs[-1]), iref, "integers, plain")
+        exact((mode, kind), p.call(outs[-1]), iref, "integers, plain", at=kind)
         if kind != 'wgrad':
             for act in ('lrelu', 'relu'):
                 outs.append(p.out())
-                exact(mode, kind, p.call(outs[-1], act, bias=True), act64(irb, act), "integers, bias + %s" % act, zero_sign=act != 'relu')
+                exact((mode, kind), p.call(outs[-1], act, bias=True), act64(irb, act), "integers, bias + %s" % act, at=kind, zero_sign=act != 'relu')
         outs.append(p.out(di['prev'][kind]))
-        exact(mode, kind, p.call(outs[-1], accumulate=True), di['prev'][kind] + iref, "integers, accumulate")
+        exact((mode, kind), p.call(outs[-1], accumulate=True), di['prev'][kind] + iref, "integers, accumulate", at=kind)
         if kind == 'dgrad':
             assert p.dact_form() == row.reaches['dact'], (p.dact_form(), row.reaches)
             if row.reaches['dact']:
                 for act in ('lrelu', 'relu'):
                     outs.append(p.out())
-                    exact(mode, kind, p.call_dact(outs[-1], act), iref * slope64(di['yact'], act), "integers, dact %s" % act)
+                    exact((mode, kind), p.call_dact(outs[-1], act), iref * slope64(di['yact'], act), "integers, dact %s" % act, at=kind)
         p.settle((R.row_id(row), "integer pass"), outs)
         # ---- 2. real pass ----
         dr = cached(('real', g), lambda: R.real_inputs(g))
@@ -404,18 +221,18 @@ def test_row(gpu, mem, row):
         p = Product(gpu, mode, kind, g, row.view, dr)
         o1, o2, o3 = p.out(), p.out(), p.out()
         got = p.call(o1, bias=kind != 'wgrad')
-        note(mode, kind, got, rb, M, "real")
+        note((mode, kind), got, rb, M, "real", at=kind)
         again = p.call(o2, bias=kind != 'wgrad')
-        exact(mode, kind, again, got, "real, repeated call")
+        exact((mode, kind), again, got, "real, repeated call", at=kind)
         inc = p.call(o3) if kind != 'wgrad' else got
         o4 = p.out(dr['prev'][kind])
         acc = p.call(o4, accumulate=True)
-        exact(mode, kind, acc, (dr['prev'][kind] + inc).astype(np.float32), "real, accumulate == fl32(previous + increment)")
+        exact((mode, kind), acc, (dr['prev'][kind] + inc).astype(np.float32), "real, accumulate == fl32(previous + increment)", at=kind)
         outs = [o1, o2, o3, o4]
         if kind == 'dgrad' and row.reaches['dact']:
             outs.append(p.out())
             s = slope64(dr['yact'], 'lrelu')
-            note(mode, kind, p.call_dact(outs[-1], 'lrelu'), r0 * s, (M - np.abs(dr['bc'].astype(np.float64))[None, :, None, None]) * s, "real, dact lrelu")
+            note((mode, kind), p.call_dact(outs[-1], 'lrelu'), r0 * s, (M - np.abs(dr['bc'].astype(np.float64))[None, :, None, None]) * s, "real, dact lrelu", at=kind)
         p.settle((R.row_id(row), "real pass"), outs)
 
 
@@ -433,26 +250,26 @@ def test_q_operands(gpu, mem, q):
     ops.q_pack(src.t, inq.q)
     inq.snapshot()
     p.inputs.append(inq)
-    for want, have in zip(R.pieces(src.data, mode), inq.values()):
+    for want, have in zip(R.pieces(src.data, mode), inq.pieces()):
         assert Q.bits_equal(have, want)
     o1, o2 = p.out(), p.out()
     y1 = p.call(o1, 'lrelu', bias=True)
-    note(mode, kind, y1, act64(rb, 'lrelu'), M, "q row, fp32 input")
+    note((mode, kind), y1, act64(rb, 'lrelu'), M, "q row, fp32 input", at=kind)
     outq = QV(gpu, R.out_shape(kind, g), mode, view)
     if kind == 'fwd':
         ops.conv2d_fwd_lp_q(p.desc, inq.q, p.w.ptr, p.bias.t, o2.t, outq.q, mode, 'lrelu', R.SLOPE)
     else:
         ops.conv2d_dgrad_lp_q(p.desc, inq.q, p.w.ptr, o2.t, outq.q, mode, p.bias.t, 'lrelu', R.SLOPE)
     y2 = o2.numpy()
-    exact(mode, kind, y2, y1, "q input == fp32 input")
-    for i, (want, have) in enumerate(zip(R.pieces(y2, mode), outq.values())):
-        exact(mode, kind, have, want, "q output piece %d == pieces(fp32 output)" % i)
+    exact((mode, kind), y2, y1, "q input == fp32 input", at=kind)
+    for i, (want, have) in enumerate(zip(R.pieces(y2, mode), outq.pieces())):
+        exact((mode, kind), have, want, "q output piece %d == pieces(fp32 output)" % i, at=kind)
     only = QV(gpu, R.out_shape(kind, g), mode, view)          # the fp32 pointer NULL: the q result is unchanged
     if kind == 'fwd':
         ops.conv2d_fwd_lp_q(p.desc, inq.q, p.w.ptr, p.bias.t, None, only.q, mode, 'lrelu', R.SLOPE)
     else:
         ops.conv2d_dgrad_lp_q(p.desc, inq.q, p.w.ptr, None, only.q, mode, p.bias.t, 'lrelu', R.SLOPE)
-    for want, have in zip(outq.values(), only.values()):
+    for want, have in zip(outq.pieces(), only.pieces()):
         assert Q.bits_equal(have, want)
     clean((q, "q outputs"), outq, only)
     p.settle((q, "q row"), [o1, o2])

@@ -41,93 +41,29 @@ distinct ring depths from a group whose budgets give two).  Wall time on the MI3
 fixture's start and end).
 """
 import ctypes as C
-import time
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import GhmError, call, tuning_env
 from oracle import lp as LP
+from tests import canary
 from tests import conv_small_ref as R
 from tests import elementwise_q_ref as Q
-from tests.test_gpu_conv_s2 import QV, V, clean, unchanged
-from tests.test_gpu_pool_bwd import Buf, repaint
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-COUNT = {}
-_REF = {}
-_T0 = [None]
 BOUND = dict(R.K_BOUND, bn=R.K_BN, mean=R.K_MEAN, inv=R.K_INV, run=R.K_RUN)
-
-
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.close()
-    _REF.clear()
-    print()
-    for key in sorted(MEASURED, key=str):
-        print("measured %-16s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)"
-              % ((" ".join(key) if isinstance(key, tuple) else key,) + MEASURED[key][:1] + (BOUND[key],) + MEASURED[key][1:] + (COUNT[key],)))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
-
-
-@pytest.fixture
-def mem(gpu):
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-def note(key, g, kind, got, ref, M, what, rel_bound=None):
-    k = BOUND[key]
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    w, r = R.worst(got, ref, M), R.rel(got, ref)
-    print("%s %s: worst k %.3f (bound %d)  rel-L2 %.2e" % (key, what, w, k, r))
-    old = MEASURED.get(key, (0.0, 0.0))
-    MEASURED[key] = (max(old[0], w), max(old[1], r))
-    COUNT[key] = COUNT.get(key, 0) + 1
-    assert np.isfinite(got).all(), (what, "the output is not finite everywhere: %d elements" % (~np.isfinite(got)).sum())
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        where = R.element_class(kind, g, i) if got.ndim == 4 else "channel"
-        pytest.fail("%s %s: element %s (%s) got %r ref %r: %.2f x 2^-24 M > k = %d" % (key, what, i, where, got[i], ref[i], w, k))
-    if rel_bound is not None:
-        assert r <= rel_bound, (what, r)
-
-
-def exact(key, g, kind, got, want, what, zero_sign=True):
-    """bit for bit; zero_sign False (relu folded into a slope: v * 0 carries v's sign): a zero of either sign is a zero"""
-    COUNT[key] = COUNT.get(key, 0) + 1
-    MEASURED.setdefault(key, (0.0, 0.0))
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    if not zero_sign:
-        got, want = np.where(got == 0, np.float32(0), got), np.where(want == 0, np.float32(0), want)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        i = tuple(bad[0])
-        where = R.element_class(kind, g, i) if got.ndim == 4 else "channel"
-        pytest.fail("%s %s: %d of %d elements differ in bits, first at %s (%s): got %r, expected %r"
-                    % (key, what, len(bad), got.size, i, where, got[i], want[i]))
+_REF = {}
+LEDGER = canary.Ledger(lambda key, w, r, n: "measured %-16s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)"
+                       % (" ".join(key) if isinstance(key, tuple) else key, w, BOUND[key], r, n),
+                       bound=BOUND.__getitem__, rel_limit=None, order=lambda m: sorted(m, key=str), header="",
+                       describe=lambda at, i, shape: R.element_class(at[0], at[1], i) if len(shape) == 4 else "channel")
+gpu, mem = canary.fixtures(LEDGER, _REF)
+cached = functools.partial(canary.cached, _REF)
+V, Buf, QV = canary.View.named, canary.Bytes, canary.QView.named
+clean, unchanged, repaint, note, exact = canary.clean, canary.unchanged, canary.repaint, LEDGER.note, LEDGER.exact
 
 
 def vec(gpu, a):
@@ -156,7 +92,7 @@ class Product:
         self.inq = QV(gpu, R.in_shape(kind, g), mode, view)
         ops.q_pack(self.src.t, self.inq.q)
         self.inq.snapshot()
-        assert Q.bits_equal(self.inq.values()[0], LP.ROUND[mode](src))
+        assert Q.bits_equal(self.inq.pieces()[0], LP.ROUND[mode](src))
         tr = kind == 'dgrad'
         wp = Buf(gpu, 4 * k * k * Cc * K, D.pack_conv_w(d['W']))
         self.wq = Buf(gpu, ops.lp_weight_bytes(self.desc, tr, mode))       # exactly the documented size
@@ -226,17 +162,17 @@ def test_row(gpu, mem, row):
                 o, oq = p.out(), p.outq()
                 want = R.act64(irb if bias else iref, act)
                 what = "integers, %s%s" % ("bias + " if bias else "", act)
-                exact(key, g, kind, p.call(o, oq, act, bias=bias), want, what, zero_sign=act != 'relu')
-                exact(key, g, kind, oq.values()[0], rnd(want), what + ": q output == round(fp32 output)", zero_sign=act != 'relu')
+                exact(key, p.call(o, oq, act, bias=bias), want, what, at=(kind, g), zero_sign=act != 'relu')
+                exact(key, oq.pieces()[0], rnd(want), what + ": q output == round(fp32 output)", at=(kind, g), zero_sign=act != 'relu')
                 if act == 'lrelu' and bias:
                     only = p.outq()
                     p.call(None, only, act, bias=True)
                     assert np.array_equal(only.raw()[only.inside], oq.raw()[oq.inside]), "the q output changes when the fp32 output is omitted"
-                    exact(key, g, kind, p.call(p.out(), None, act, bias=True, fp32_operand=True), want, what + ", fp32 operand")
+                    exact(key, p.call(p.out(), None, act, bias=True, fp32_operand=True), want, what + ", fp32 operand", at=(kind, g))
         o, oq = p.out(di['prev'][kind]), p.outq()
         acc = di['prev'][kind] + irb
-        exact(key, g, kind, p.call(o, oq, bias=True, accumulate=True), acc, "integers, accumulate")
-        exact(key, g, kind, oq.values()[0], rnd(acc), "integers, accumulate: q output")
+        exact(key, p.call(o, oq, bias=True, accumulate=True), acc, "integers, accumulate", at=(kind, g))
+        exact(key, oq.pieces()[0], rnd(acc), "integers, accumulate: q output", at=(kind, g))
         p.settle((R.row_id(row), "integer pass"))
         # ---- 2. real pass ----
         dr = cached(('real', g), lambda: R.real_inputs(g))
@@ -246,23 +182,22 @@ def test_row(gpu, mem, row):
         p = Product(gpu, mode, kind, g, row.view, dr)
         o1, q1 = p.out(), p.outq()
         got = p.call(o1, q1, bias=True)
-        note(key, g, kind, got, ref, M, "real", R.REL_L2[mode])
-        exact(key, g, kind, q1.values()[0], rnd(got), "real: q output == round(fp32 output)")
+        note(key, got, ref, M, "real", at=(kind, g), rel_limit=R.REL_L2[mode])
+        exact(key, q1.pieces()[0], rnd(got), "real: q output == round(fp32 output)", at=(kind, g))
         o2, q2 = p.out(), p.outq()
-        exact(key, g, kind, p.call(o2, q2, bias=True), got, "real, repeated call")
+        exact(key, p.call(o2, q2, bias=True), got, "real, repeated call", at=(kind, g))
         assert np.array_equal(q2.raw()[q2.inside], q1.raw()[q1.inside])
-        exact(key, g, kind, p.call(p.out(), None, bias=True, fp32_operand=True), got, "real, fp32 operand == q operand")
+        exact(key, p.call(p.out(), None, bias=True, fp32_operand=True), got, "real, fp32 operand == q operand", at=(kind, g))
         o4 = p.out(dr['prev'][kind])
-        exact(key, g, kind, p.call(o4, None, bias=True, accumulate=True), (dr['prev'][kind] + got).astype(np.float32),
-              "real, accumulate == fl32(previous + finished sum)")
+        exact(key, p.call(o4, None, bias=True, accumulate=True), (dr['prev'][kind] + got).astype(np.float32), "real, accumulate == fl32(previous + finished sum)", at=(kind, g))
         unchanged((R.row_id(row), "real pass"), *p.inputs)
         clean((R.row_id(row), "real pass"), *p.outs)
         # ---- 3. nothing outside the views is read: the same bits over a finite pattern ----
         o5, q5 = p.out(), p.outq()
         repaint(dev, *p.everything())
-        exact(key, g, kind, p.call(o5, q5, bias=True), got, "real, everything outside the views repainted")
+        exact(key, p.call(o5, q5, bias=True), got, "real, everything outside the views repainted", at=(kind, g))
         assert np.array_equal(q5.raw()[q5.inside], q1.raw()[q1.inside])
-        exact(key, g, kind, p.call(p.out(), None, bias=True, fp32_operand=True), got, "real, repainted, fp32 operand")
+        exact(key, p.call(p.out(), None, bias=True, fp32_operand=True), got, "real, repainted, fp32 operand", at=(kind, g))
 
 
 RING_GROUPS = [(kind, g, [dict(R.SPLIT1, GHM_SM_LDS_KB=str(kb)) for kb in R.RING_KB]) for kind, g in R.RING_SHAPES] + \
@@ -284,7 +219,7 @@ def test_every_ring_depth_gives_the_same_bits(gpu, mem, group, mode):
             got = p.call(p.out(), None, bias=True)
         if first is None:
             first = got
-        exact((mode, kind), g, kind, got, first, "ring budget %s KB against %s KB" % (env['GHM_SM_LDS_KB'], envs[0]['GHM_SM_LDS_KB']))
+        exact((mode, kind), got, first, "ring budget %s KB against %s KB" % (env['GHM_SM_LDS_KB'], envs[0]['GHM_SM_LDS_KB']), at=(kind, g))
     assert len(depths) >= 2, depths
     p.settle((group[:2], mode, "ring depths"))
 
@@ -338,43 +273,42 @@ def test_batchnorm_row(gpu, mem, case):
 
         o = run('lrelu', True)
         t = o['co'].numpy()
-        note(key, g, 'fwd', t, ref, M, "BatchNorm row: conv_out", R.REL_L2.get(mode, 1e-5))
-        exact(key, g, 'fwd', t[:, z], np.broadcast_to(d['b'][z], t[:, z].shape), "conv_out of the all-zero filter == bias")
+        note(key, t, ref, M, "BatchNorm row: conv_out", at=('fwd', g), rel_limit=R.REL_L2.get(mode, 1e-5))
+        exact(key, t[:, z], np.broadcast_to(d['b'][z], t[:, z].shape), "conv_out of the all-zero filter == bias", at=('fwd', g))
         want = R.bn_ref(t, d, 'lrelu', R.BN_SLOPE)
-        y, mean, inv = o['y'].numpy(), o['mean'].f32(), o['inv'].f32()
-        note('bn', g, 'fwd', y, want['y'], want['M'], "y")
-        note('mean', g, 'fwd', mean, want['mean'], want['M_mean'], "mean")
-        note('inv', g, 'fwd', inv, want['inv'], want['inv'], "inv")
-        note('run', g, 'fwd', o['rm'].f32(), want['rm'], want['M_rm'], "running mean")
-        note('run', g, 'fwd', o['ri'].f32(), want['ri'], want['M_ri'], "running inverse std")
+        y, mean, inv = o['y'].numpy(), o['mean'].numpy(), o['inv'].numpy()
+        note('bn', y, want['y'], want['M'], "y", at=('fwd', g))
+        note('mean', mean, want['mean'], want['M_mean'], "mean", at=('fwd', g))
+        note('inv', inv, want['inv'], want['inv'], "inv", at=('fwd', g))
+        note('run', o['rm'].numpy(), want['rm'], want['M_rm'], "running mean", at=('fwd', g))
+        note('run', o['ri'].numpy(), want['ri'], want['M_ri'], "running inverse std", at=('fwd', g))
         if o['yq'] is not None:
-            exact('bn', g, 'fwd', o['yq'].values()[0], rnd(y), "q output == round(y)")
+            exact('bn', o['yq'].pieces()[0], rnd(y), "q output == round(y)", at=('fwd', g))
         # the all-zero filter: zero variance (the var < 0 clamp's neighbourhood)
         assert mean[z] == d['b'][z] and inv[z] == np.float32(1.0 / np.sqrt(float(np.float32(R.BN_EPS)))), (mean[z], inv[z])
         beta_z = np.float32(d['beta'][z])
-        exact('bn', g, 'fwd', y[:, z], np.broadcast_to(beta_z if beta_z > 0 else np.float32(R.BN_SLOPE) * beta_z, y[:, z].shape),
-              "y of the all-zero filter == act(beta)")
+        exact('bn', y[:, z], np.broadcast_to(beta_z if beta_z > 0 else np.float32(R.BN_SLOPE) * beta_z, y[:, z].shape), "y of the all-zero filter == act(beta)", at=('fwd', g))
         outs = [v for v in o.values() if v is not None]
         unchanged((R.bn_row_id(row), mode), *inputs)
         clean((R.bn_row_id(row), mode), *outs)
         # no running statistics passed: theirs stay as they were; the q output alone; linear
         o2 = run('lrelu', False, want_y=mode == 'f32')
         assert o2['rm'].same() and o2['ri'].same(), "running statistics written without being passed"
-        exact(key, g, 'fwd', o2['co'].numpy(), t, "repeated call: conv_out")
-        exact('mean', g, 'fwd', o2['mean'].f32(), mean, "repeated call: mean")
-        exact('inv', g, 'fwd', o2['inv'].f32(), inv, "repeated call: inv")
+        exact(key, o2['co'].numpy(), t, "repeated call: conv_out", at=('fwd', g))
+        exact('mean', o2['mean'].numpy(), mean, "repeated call: mean", at=('fwd', g))
+        exact('inv', o2['inv'].numpy(), inv, "repeated call: inv", at=('fwd', g))
         if o2['yq'] is not None:
             assert np.array_equal(o2['yq'].raw()[o2['yq'].inside], o['yq'].raw()[o['yq'].inside]), "the q output changes without y"
         o3 = run('linear', True, want_q=False)
-        note('bn', g, 'fwd', o3['y'].numpy(), R.bn_ref(t, d, 'linear')['y'], want['M'], "y, linear")
+        note('bn', o3['y'].numpy(), R.bn_ref(t, d, 'linear')['y'], want['M'], "y, linear", at=('fwd', g))
         outs += [v for oo in (o2, o3) for v in oo.values() if v is not None]
         clean((R.bn_row_id(row), mode, "second and third call"), *outs)
         # nothing outside the views is read
         repaint(dev, *(inputs + outs))
         o4 = run('lrelu', True)
-        exact('bn', g, 'fwd', o4['y'].numpy(), y, "everything outside the views repainted: y")
-        exact(key, g, 'fwd', o4['co'].numpy(), t, "repainted: conv_out")
-        exact('run', g, 'fwd', o4['rm'].f32(), o['rm'].f32(), "repainted: running mean")
+        exact('bn', o4['y'].numpy(), y, "everything outside the views repainted: y", at=('fwd', g))
+        exact(key, o4['co'].numpy(), t, "repainted: conv_out", at=('fwd', g))
+        exact('run', o4['rm'].numpy(), o['rm'].numpy(), "repainted: running mean", at=('fwd', g))
         clean((R.bn_row_id(row), mode, "repainted"), *[v for v in o4.values() if v is not None])
 
 

@@ -53,95 +53,29 @@ kernel then stands 4.03, 4.07, 3.76 and 2.65 units from the reference and, for o
 bits, as igemm_kernel on one input channel does for the forward.  Library changes: that, and the alignment guard of the three
 fan-out predicates.
 """
-import collections
-import time
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import GhmError, tuning_env
+from tests import canary
 from tests import conv_thin_ref as R
 from tests import elementwise_q_ref as Q
 from tests.elementwise_f32_ref import K_LIBM
-from tests.test_gpu_conv_s2 import QV, Raw, V, clean, unchanged
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-COUNT = {}
 TANH = [0.0]
-_REF = collections.OrderedDict()
-_T0 = [None]
-
-
-def cached(key, fn, keep=10):
-    """the float64 references per geometry, shared by the rows that follow each other; the oldest leave (they are 16 - 70 MB)"""
-    if key not in _REF:
-        _REF[key] = fn()
-        while len(_REF) > keep:
-            _REF.popitem(last=False)
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.close()
-    _REF.clear()
-    for key in sorted(MEASURED):
-        print("measured %-10s %-6s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)"
-              % (key + MEASURED[key][:1] + (R.K_BOUND[key],) + MEASURED[key][1:] + (COUNT[key],)))
-    print("tanh: worst %.3f of %d units of max(|tanh|, 2^-126)" % (TANH[0], K_LIBM['in_fwd_tanh']))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
-
-
-@pytest.fixture
-def mem(gpu):
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-def note(key, kind, g, got, ref, M, what, factor=1):
-    k = factor * R.K_BOUND[key]
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    w, r = R.worst(got, ref, M), R.rel(got, ref)
-    print("%s %s %s: worst k %.3f (bound %d)  rel-L2 %.2e" % (key + (what, w, k, r)))
-    if factor == 1:
-        old = MEASURED.get(key, (0.0, 0.0))
-        MEASURED[key] = (max(old[0], w), max(old[1], r))
-    COUNT[key] = COUNT.get(key, 0) + 1
-    assert np.isfinite(got).all(), (what, "the output is not finite everywhere: %d elements" % (~np.isfinite(got)).sum())
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s %s: element %s (%s) got %r ref %r: %.2f x 2^-24 M > k = %d"
-                    % (key + (what, i, R.border_class(kind, g, i), got[i], ref[i], w, k)))
-    assert r <= R.REL_L2, (what, r)
-
-
-def exact(key, kind, g, got, want, what, zero_sign=True):
-    """bit for bit; zero_sign False: a zero of either sign is a zero (relu: the epilogues that fold it into a piece-wise linear
-    slope return v * 0 = -0 for a negative v, the others max(v, 0) = +0)"""
-    COUNT[key] = COUNT.get(key, 0) + 1
-    MEASURED.setdefault(key, (0.0, 0.0))
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape
-    if not zero_sign:
-        got, want = np.where(got == 0, np.float32(0), got), np.where(want == 0, np.float32(0), want)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        i = tuple(bad[0])
-        pytest.fail("%s %s %s: %d of %d elements differ in bits, first at %s (%s): got %r, expected %r"
-                    % (key + (what, len(bad), got.size, i, R.border_class(kind, g, i), got[i], want[i])))
+_REF = {}
+LEDGER = canary.Ledger(lambda key, w, r, n: "measured %-10s %-6s worst k %7.3f of %2d  rel-L2 %.2e  (%d comparisons)" % (key + (w, R.K_BOUND[key], r, n)),
+                       bound=R.K_BOUND.__getitem__, rel_limit=R.REL_L2, describe=lambda at, i, shape: R.border_class(at[0], at[1], i),
+                       footer=lambda: "tanh: worst %.3f of %d units of max(|tanh|, 2^-126)" % (TANH[0], K_LIBM['in_fwd_tanh']))
+gpu, mem = canary.fixtures(LEDGER, _REF)
+# the float64 references per geometry, shared by the rows that follow each other; the oldest leave (they are 16 - 70 MB)
+cached = functools.partial(canary.cached, _REF, keep=10)
+V, Raw, QV = canary.View.named, canary.Bytes.rounded, canary.QView.named
+clean, unchanged, note, exact = canary.clean, canary.unchanged, LEDGER.note, LEDGER.exact
 
 
 class Product:
@@ -215,7 +149,7 @@ class Product:
         unchanged(what, *self.inputs)
         clean(what, *(self.buffers + outs))
         for o in outs:
-            self.gpu[0].free(o.ptr if isinstance(o, V) else o.base)
+            self.gpu[0].free(o.base)
 
 
 def refs(kind, g, d, key):
@@ -250,13 +184,13 @@ def test_row(gpu, mem, row):
         prev = di['prev'][R.base_kind(kind)]
         p = Product(gpu, kind, g, row.view, di)
         outs = [p.out()]
-        exact(key, kind, g, p.call(outs[-1]), iref, "integers, plain")
+        exact(key, p.call(outs[-1]), iref, "integers, plain", at=(kind, g))
         if lin:
             for act in ('lrelu', 'relu'):
                 outs.append(p.out())
-                exact(key, kind, g, p.call(outs[-1], act, bias=True), R.act64(irb, act), "integers, bias + %s" % act, zero_sign=act != 'relu')
+                exact(key, p.call(outs[-1], act, bias=True), R.act64(irb, act), "integers, bias + %s" % act, at=(kind, g), zero_sign=act != 'relu')
         outs.append(p.out(prev))
-        exact(key, kind, g, p.call(outs[-1], accumulate=True), prev + iref, "integers, accumulate")
+        exact(key, p.call(outs[-1], accumulate=True), prev + iref, "integers, accumulate", at=(kind, g))
         p.settle((R.row_id(row), "integer pass"), outs)
         # ---- 2. real pass ----
         dr = cached(('real', g), lambda: R.real_inputs(g))
@@ -265,10 +199,10 @@ def test_row(gpu, mem, row):
         p = Product(gpu, kind, g, row.view, dr)
         o1, o2, o3, o4 = p.out(), p.out(), p.out(), p.out(prev)
         got = p.call(o1, bias=lin)
-        note(key, kind, g, got, rb, M, "real")
-        exact(key, kind, g, p.call(o2, bias=lin), got, "real, repeated call")
+        note(key, got, rb, M, "real", at=(kind, g))
+        exact(key, p.call(o2, bias=lin), got, "real, repeated call", at=(kind, g))
         inc = p.call(o3) if lin else got
-        exact(key, kind, g, p.call(o4, accumulate=True), (prev + inc).astype(np.float32), "real, accumulate == fl32(previous + increment)")
+        exact(key, p.call(o4, accumulate=True), (prev + inc).astype(np.float32), "real, accumulate == fl32(previous + increment)", at=(kind, g))
         outs = [o1, o2, o3, o4]
         if row.kernel == 'fanin_s1' and kind == 'fwd' and g == (2, 64, 128, 128, 1, 5, 1, 2):      # g_out's own activation
             outs.append(p.out())
@@ -295,7 +229,7 @@ def test_row_agrees_with_the_general_kernel(gpu, mem, row):
     with tuning_env(**dict(row.env, GHM_NO_THIN='1')):
         general = p.call(o2, bias=lin)
     print("%s: the general kernel stands %.3f x 2^-24 M from the reference, the thin kernel %.3f" % (R.row_id(row), R.worst(general, rb, M), R.worst(thin, rb, M)))
-    note(key, kind, g, thin, general.astype(np.float64), M, "real, against GHM_NO_THIN=1", factor=2)
+    note(key, thin, general.astype(np.float64), M, "real, against GHM_NO_THIN=1", at=(kind, g), k=2 * R.K_BOUND[key], record=False)
     p.settle((R.row_id(row), "general kernel"), [o1, o2])
 
 
@@ -314,7 +248,7 @@ def test_pooled_row(gpu, mem, row):
             assert tied > 0.01, "the integer inputs must produce tied windows"
             o, m = p.out(), p.mask()
             pooled, mask = p.call_pool(o, m, act)
-            exact(key, 'pool', g, pooled, want, "integers, pooled bias + %s" % act, zero_sign=act != 'relu')
+            exact(key, pooled, want, "integers, pooled bias + %s" % act, at=('pool', g), zero_sign=act != 'relu')
             assert np.array_equal(mask, wmask), ("integers, %s: %d mask bytes differ (%.0f %% of the windows are tied)"
                                                  % (act, (mask != wmask).sum(), 100 * tied))
             outs += [o, m]
@@ -324,15 +258,15 @@ def test_pooled_row(gpu, mem, row):
         p = Product(gpu, 'pool', g, row.view, dr)
         o1, m1, o2, m2 = p.out(), p.mask(), p.out(), p.mask()
         pooled, mask = p.call_pool(o1, m1, 'lrelu')
-        note(key, 'pool', g, pooled, R.pool_ref(R.act64(rb, 'lrelu'))[0], R.pool_ref(M)[0], "real, pooled")
+        note(key, pooled, R.pool_ref(R.act64(rb, 'lrelu'))[0], R.pool_ref(M)[0], "real, pooled", at=('pool', g))
         again, mask2 = p.call_pool(o2, m2, 'lrelu')
-        exact(key, 'pool', g, again, pooled, "real, repeated call")
+        exact(key, again, pooled, "real, repeated call", at=('pool', g))
         assert np.array_equal(mask, mask2)
         # the unpooled fan-out forward of the same inputs, pooled on the host: the same accumulators, so the same bits and mask
         full = V(gpu, R.shapes(g)[2], 'whole')
         gpu[1].conv2d_fwd(p.desc, p.x.t, p.w.t, p.bias.t, full.t, 'lrelu', R.SLOPE)
         want, wmask = R.pool_ref(full.numpy())
-        exact(key, 'pool', g, pooled, want, "real, pooled == max-pool of the unpooled forward")
+        exact(key, pooled, want, "real, pooled == max-pool of the unpooled forward", at=('pool', g))
         assert np.array_equal(mask, wmask)
         p.settle((R.row_id(row), "real pass"), [o1, m1, o2, m2, full])
 
@@ -369,10 +303,10 @@ def test_q_epilogue(gpu, mem, q, mode):
                 assert np.array_equal(p.mask_bytes(m1), mask0) and np.array_equal(p.mask_bytes(m2), mask0)
                 outs += [m1, m2]
             y = o.numpy()
-            exact(key, kind, g, y, y0, "%s %s: fp32 output of the q call == the plain call" % (mode, view))
-            for i, (want, have, alone) in enumerate(zip(R.pieces(y, mode), outq.values(), only.values())):
-                exact(key, kind, g, have, want, "%s %s: q piece %d == pieces(fp32 output)" % (mode, view, i))
-                exact(key, kind, g, alone, want, "%s %s: q-only piece %d" % (mode, view, i))
+            exact(key, y, y0, "%s %s: fp32 output of the q call == the plain call" % (mode, view), at=(kind, g))
+            for i, (want, have, alone) in enumerate(zip(R.pieces(y, mode), outq.pieces(), only.pieces())):
+                exact(key, have, want, "%s %s: q piece %d == pieces(fp32 output)" % (mode, view, i), at=(kind, g))
+                exact(key, alone, want, "%s %s: q-only piece %d" % (mode, view, i), at=(kind, g))
             clean((q, mode, view, "q outputs"), outq, only)
             outs.append(o)
             for t in (outq, only):
@@ -400,9 +334,9 @@ def test_output_four_bytes_in_is_not_given_to_the_vector_stores(gpu, mem, entry)
     p = Product(gpu, kind, g, 'whole', di, out_view='off4')
     outs = [p.out(), p.out(), p.out(di['prev'][R.base_kind(kind)])]
     assert outs[0].t.ptr % 16 == 4
-    exact(key, kind, g, p.call(outs[0]), iref, "4 bytes in: integers, plain")
-    exact(key, kind, g, p.call(outs[1], 'lrelu', bias=True), R.act64(irb, 'lrelu'), "4 bytes in: integers, bias + lrelu")
-    exact(key, kind, g, p.call(outs[2], accumulate=True), di['prev'][R.base_kind(kind)] + iref, "4 bytes in: integers, accumulate")
+    exact(key, p.call(outs[0]), iref, "4 bytes in: integers, plain", at=(kind, g))
+    exact(key, p.call(outs[1], 'lrelu', bias=True), R.act64(irb, 'lrelu'), "4 bytes in: integers, bias + lrelu", at=(kind, g))
+    exact(key, p.call(outs[2], accumulate=True), di['prev'][R.base_kind(kind)] + iref, "4 bytes in: integers, accumulate", at=(kind, g))
     p.settle((entry, "integer pass"), outs)
     r0, rb, M = refs(kind, g, dr, 'real')
     p = Product(gpu, kind, g, 'whole', dr, out_view='off4')
@@ -412,7 +346,7 @@ def test_output_four_bytes_in_is_not_given_to_the_vector_stores(gpu, mem, entry)
     thin = p.call(o3, bias=True)                        # the aligned view: the thin kernel
     with tuning_env(GHM_NO_THIN='1'):
         general = p.call(o2, bias=True)
-    exact(key, kind, g, got, general, "4 bytes in: the general kernel's bits")
+    exact(key, got, general, "4 bytes in: the general kernel's bits", at=(kind, g))
     # (the bits cannot say WHICH kernel ran: igemm_kernel and the one-thread-per-pixel data gradient run the same fmaf steps in the
     # same order as fanout_kernel's MFMAs and add the bias last, as it does.  What this row holds is that the call is served, right
     # to the bit of the general kernel, with nothing written outside the view 4 bytes in)

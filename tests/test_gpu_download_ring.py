@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from gan_heightmaps_amd.streaming import DownloadRing, store_rows
-from tests.test_gpu_texture import dev      # noqa: F401  (the module-scoped fixture)
+from tests.gpu_common import dev      # noqa: F401  (dev: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 

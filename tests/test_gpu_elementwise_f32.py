@@ -51,130 +51,24 @@ ghm_maxpool2_mask_bwd(_bias) in fp32: tests/test_gpu_ops.py already reaches both
 test_conv_lrelu_maxpool_fused and four cases of test_conv_pool_backward_from_the_pooled_operands have per_plane % 256 == 0
 (the in-kernel partial sums), the case (2, 32, 64, 72) has per_plane = 576 (two passes) -- so no row is added for it.
 """
-import time
+import functools
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import GhmError
+from tests import canary
 from tests import elementwise_f32_ref as R
 
 pytestmark = pytest.mark.gpu
 
 A = R.ALPHA
-MEASURED = {}
-COUNT = {}
 _REF = {}
-_T0 = [None]
-
-
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.set_loss_scale_state(None)
-    dev.close()
-    _REF.clear()
-    for op in sorted(MEASURED):
-        print("measured %-22s worst k %7.3f  rel-L2 %.2e  (%d comparisons)" % ((op,) + MEASURED[op] + (COUNT[op],)))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
-
-
-@pytest.fixture
-def mem(gpu):
-    """frees what a test allocated, and leaves no loss-scale state attached"""
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.set_loss_scale_state(None)
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-class V:
-    """an fp32 tensor whose surroundings hold the canary: ``el0`` elements into the allocation, ``extra`` elements between the
-    samples, a tail behind the last one (the F32 of tests/test_gpu_elementwise_q.py with the offset and the stride free)"""
-
-    def __init__(self, gpu, shape, spec=(0, 0), data=None):
-        self.dev, _, D = gpu
-        if len(shape) == 1:
-            shape = (1, shape[0], 1, 1)
-        N, C, H, W = shape
-        chw = C * H * W
-        el0, ns = spec[0], chw + spec[1]
-        self.total = el0 + (N - 1) * ns + chw + 8
-        self.ptr = self.dev.alloc(4 * self.total)
-        assert self.ptr % 16 == 0
-        R.canary_fill(self.dev, self.ptr, 4 * self.total)
-        self.t = D.DevTensor(self.dev, self.ptr + 4 * el0, shape, ns)
-        self.inside = R.f32_inside(N, ns, el0, chw, self.total)
-        self.data = None
-        if data is not None:
-            self.set(data)
-
-    def set(self, data):
-        self.data = np.ascontiguousarray(data, np.float32).reshape(self.t.shape).copy()
-        self.t.set(self.data)
-        return self
-
-    def numpy(self):
-        return self.t.numpy()
-
-    def stray(self):
-        return R.canary_changed(self.dev, self.ptr, 4 * self.total, self.inside)
-
-
-def clean(what, *views):
-    """assertion 2: no canary changed round any view; a view that was given data and not written still holds it"""
-    for i, v in enumerate(views):
-        s = v.stray()
-        assert s.size == 0, (what, "view %d: %d halfwords outside it were written, first at element %d" % (i, s.size, s[0] // 2 if s.size else -1))
-
-
-def unchanged(what, *views):
-    clean(what, *views)
-    for i, v in enumerate(views):
-        assert R.bits_equal(v.numpy(), np.reshape(v.data, v.t.shape)), (what, "input %d was modified" % i)
-
-
-def note(op, got, ref, M, k, what):
-    """assertion 1, with the figures printed before they are asserted and kept for the summary"""
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    w, r = R.worst(got, ref, M), R.rel(got, ref)
-    print("%s %s: worst k %.3f (bound %s)  rel-L2 %.2e" % (op, what, w, k, r))
-    old = MEASURED.get(op, (0.0, 0.0))
-    MEASURED[op] = (max(old[0], w), max(old[1], r))
-    COUNT[op] = COUNT.get(op, 0) + 1
-    assert np.isfinite(got).all(), (op, what)
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s: element %s got %r ref %r: %.2f x 2^-24 M > k = %s" % (op, what, i, got[i], ref[i], w, k))
-    assert r <= R.REL_L2, (op, what, r)
-
-
-def exact(op, got, want, what):
-    COUNT[op] = COUNT.get(op, 0) + 1
-    MEASURED.setdefault(op, (0.0, 0.0))
-    if not R.bits_equal(got, want):
-        bad = np.argwhere(np.ascontiguousarray(got, np.float32).view(np.uint32) != np.ascontiguousarray(want, np.float32).view(np.uint32))
-        i = tuple(bad[0])
-        pytest.fail("%s %s: %d elements differ in bits, first %s: got %r, expected %r" % (op, what, len(bad), i, got[i], want[i]))
-
-
-def fl32_sum(prev, inc):
-    return (np.asarray(prev, np.float32) + np.asarray(inc, np.float32)).astype(np.float32)
+LEDGER = canary.Ledger(lambda op, w, r, n: "measured %-22s worst k %7.3f  rel-L2 %.2e  (%d comparisons)" % (op, w, r, n))
+gpu, mem = canary.fixtures(LEDGER, _REF, loss_scale=True)
+cached = functools.partial(canary.cached, _REF)
+V, clean, unchanged, fl32_sum = canary.View.free, canary.clean, canary.unchanged, canary.fl32_sum
+note, exact = LEDGER.note, LEDGER.exact
 
 
 def scalar(t):
@@ -192,7 +86,7 @@ def test_maxpool2(gpu, mem, shape, why):
     x, y = V(gpu, shape, data=d['x']), V(gpu, ps)
     ops.maxpool2_fwd(x.t, y.t)
     y32 = y.numpy()
-    COUNT['maxpool2_fwd'] = COUNT.get('maxpool2_fwd', 0) + 1
+    LEDGER.tally('maxpool2_fwd')
     assert R.maxpool_selects(y32, d['x']), (shape, "an output is not an element of its window equal to the window's maximum")
     yref = R.maxpool_fwd(d['x'])
     assert np.array_equal(y32, yref)
@@ -208,7 +102,7 @@ def test_maxpool2(gpu, mem, shape, why):
         dx = V(gpu, shape)
         ops.maxpool2_bwd(x.t, yin.t, dy.t, dx.t, act, A)
         got = dx.numpy()
-        note('maxpool2_bwd', got, ref, M, R.K_MAXPOOL_BWD[act], what)
+        note('maxpool2_bwd', got, ref, M, what, k=R.K_MAXPOOL_BWD[act])
         if act == 'linear':
             exact('maxpool2_bwd', got, ref.astype(np.float32), what)
         elif act == 'relu':
@@ -245,7 +139,7 @@ def test_avgpool(gpu, mem, row, why):
     ref, M = R.avgpool_fwd(xin, p)
     x, y = V(gpu, shape, data=xin), V(gpu, ps)
     ops.avgpool_fwd(x.t, y.t, p)
-    note('avgpool_fwd', y.numpy(), ref, M, R.k_avgpool_fwd(p), str(row))
+    note('avgpool_fwd', y.numpy(), ref, M, str(row), k=R.k_avgpool_fwd(p))
     clean(row, y)
     unchanged(row, x)
     g = R.Q._rng(ps, 5).randn(*ps).astype(np.float32)
@@ -253,7 +147,7 @@ def test_avgpool(gpu, mem, row, why):
     dy, dx = V(gpu, ps, data=g), V(gpu, shape)
     ops.avgpool_bwd(dy.t, dx.t, p)
     got = dx.numpy()
-    note('avgpool_bwd', got, dref, Md, R.K_AVGPOOL_BWD, str(row))
+    note('avgpool_bwd', got, dref, Md, str(row), k=R.K_AVGPOOL_BWD)
     border = np.ones(shape, bool)
     border[:, :, :H // p * p, :W // p * p] = False
     assert not got[border].any() and not np.signbit(got[border]).any(), (row, "the border is zero-filled")
@@ -281,8 +175,8 @@ def test_upsample_nearest_and_bilinear(gpu, mem, row, why):
     ops.upsample_bilinear2_fwd(x.t, y2.t)
     lit, closed, M = cached(('bil_fwd', shape), lambda: R.bilinear_fwd(d['x']))
     y32 = y2.numpy()
-    note('bilinear2_fwd', y32, lit, M, R.K_BILINEAR_FWD, what + " (Theano's algorithm)")
-    note('bilinear2_fwd', y32, closed, M, R.K_BILINEAR_FWD, what + " (closed form)")
+    note('bilinear2_fwd', y32, lit, M, what + " (Theano's algorithm)", k=R.K_BILINEAR_FWD)
+    note('bilinear2_fwd', y32, closed, M, what + " (closed form)", k=R.K_BILINEAR_FWD)
     clean(what, y2)
     unchanged(what, x)
     for t in (y, y2):
@@ -294,13 +188,13 @@ def test_upsample_nearest_and_bilinear(gpu, mem, row, why):
         dx = V(gpu, shape, vd)
         fn(g.t, dx.t)
         inc = dx.numpy()
-        note(op, inc, ref, Md, k, what)
+        note(op, inc, ref, Md, what, k=k)
         clean(what, dx)
         dx.set(d['prev'])
         fn(g.t, dx.t, accumulate=True)
         acc = dx.numpy()
         exact(op, acc, fl32_sum(d['prev'], inc), what + " accumulate")
-        note(op, acc, ref + d['prev'], Md + np.abs(d['prev']), k + 1, what + " accumulate")
+        note(op, acc, ref + d['prev'], Md + np.abs(d['prev']), what + " accumulate", k=k + 1)
         clean(what + " accumulate", dx)
         unchanged(what, g)
         dev.free(dx.ptr)
@@ -321,8 +215,8 @@ def test_scalar_losses(gpu, mem, n, why, kind):
     l1, Ml1, g1, Mg1 = R.scalar_loss(data, 1.0, kind, 0.5)
     fn(d.t, 1.0, out.t, grad.t, 0.5)
     got_l1, got_g1 = scalar(out), grad.numpy()
-    note(kind + '_loss', [got_l1], [l1], [Ml1], kl, what + " target 1")
-    note(kind + '_grad', got_g1.ravel(), g1.ravel(), Mg1.ravel(), kg, what + " target 1")
+    note(kind + '_loss', [got_l1], [l1], [Ml1], what + " target 1", k=kl)
+    note(kind + '_grad', got_g1.ravel(), g1.ravel(), Mg1.ravel(), what + " target 1", k=kg)
     clean(what, grad, out)
     unchanged(what, d)
     # target 0, no gradient buffer: the loss alone, then accumulated onto the first
@@ -330,14 +224,14 @@ def test_scalar_losses(gpu, mem, n, why, kind):
     out0 = V(gpu, (1,), data=[-7.0])
     fn(d.t, 0.0, out0.t, None, 1.0)
     got_l0 = scalar(out0)
-    note(kind + '_loss', [got_l0], [l0], [Ml0], kl, what + " target 0")
+    note(kind + '_loss', [got_l0], [l0], [Ml0], what + " target 0", k=kl)
     fn(d.t, 0.0, out.t, None, 1.0, accumulate_loss=True)
     exact(kind + '_loss', out.numpy(), fl32_sum([got_l1], [got_l0]).reshape(1, 1, 1, 1), what + " accumulate_loss")
     assert R.bits_equal(grad.numpy(), got_g1), (what, "grad = None must leave the earlier buffer alone")
     clean(what, grad, out, out0)
     # target 0 with a gradient
     fn(d.t, 0.0, out0.t, grad.t, 0.5)
-    note(kind + '_grad', grad.numpy().ravel(), 0.5 * g0.ravel(), 0.5 * Mg0.ravel(), kg, what + " target 0")
+    note(kind + '_grad', grad.numpy().ravel(), 0.5 * g0.ravel(), 0.5 * Mg0.ravel(), what + " target 0", k=kg)
     exact(kind + '_loss', out0.numpy(), np.float32(got_l0).reshape(1, 1, 1, 1), what + " same loss with a gradient")
     # a loss-scale state: the gradient times ls[0] (a power of two: exactly), the loss unscaled
     ls_host = np.array([2.0 ** 10, 2.0 ** -10, 5, 0, 2, 0, 0, 0], np.float32)
@@ -366,8 +260,8 @@ def test_recon_loss(gpu, mem, row, why):
     a, b, g, out = V(gpu, shape, va, data['a']), V(gpu, shape, vb, data['b']), V(gpu, shape, vg), V(gpu, (1,), data=[55.0])
     ops.recon_loss(a.t, b.t, out.t, g.t, gs, l2=l2)
     got_l, inc = scalar(out), g.numpy()
-    note('recon_loss', [got_l], [loss], [loss], R.K_LOSS, what)
-    note('recon_grad', inc, gref, Mg, R.K_RECON_GRAD, what)
+    note('recon_loss', [got_l], [loss], [loss], what, k=R.K_LOSS)
+    note('recon_grad', inc, gref, Mg, what, k=R.K_RECON_GRAD)
     eq = data['a'] == data['b']
     assert eq.any() and not inc[eq].any(), (what, "a == b must give a zero gradient")
     clean(what, g, out)
@@ -384,7 +278,7 @@ def test_recon_loss(gpu, mem, row, why):
     if R.recon_vec(shape[1], shape[2] * shape[3], R.view_of(shape, va), R.view_of(shape, vb), None) == \
             R.recon_vec(shape[1], shape[2] * shape[3], R.view_of(shape, va), R.view_of(shape, vb), R.view_of(shape, vg)):
         exact('recon_loss', out.numpy(), np.float32(got_l).reshape(1, 1, 1, 1), what + " grad = None")
-    note('recon_loss', [scalar(out)], [loss], [loss], R.K_LOSS, what + " grad = None")
+    note('recon_loss', [scalar(out)], [loss], [loss], what + " grad = None", k=R.K_LOSS)
     # loss-scale state
     ls = V(gpu, (8,), data=np.array([2.0 ** 7, 2.0 ** -7, 0, 0, 0, 0, 0, 0], np.float32))
     dev.set_loss_scale_state(ls.t)
@@ -411,8 +305,8 @@ def test_rmsprop_and_adam_one_launch(gpu, mem, n, why):
     rho, eps = R.RMSPROP_CONSTS
     ops.rmsprop(p.t, g.t, acc.t, n, hyper.t, rho, eps, 0.5)
     p2, Mp, a2, Ma = R.rmsprop(d['p'], d['g'], d['acc'], lr, rho, eps, 0.5)
-    note('rmsprop_acc', acc.numpy().ravel(), a2, Ma, R.K_RMSPROP_ACC, "n = %d" % n)
-    note('rmsprop_p', p.numpy().ravel(), p2, Mp, R.K_RMSPROP_P, "n = %d" % n)
+    note('rmsprop_acc', acc.numpy().ravel(), a2, Ma, "n = %d" % n, k=R.K_RMSPROP_ACC)
+    note('rmsprop_p', p.numpy().ravel(), p2, Mp, "n = %d" % n, k=R.K_RMSPROP_P)
     assert R.rel(p.numpy().ravel() - d['p'], p2 - d['p']) <= R.REL_L2
     clean(n, p, acc)
     unchanged(n, g, hyper)
@@ -423,9 +317,9 @@ def test_rmsprop_and_adam_one_launch(gpu, mem, n, why):
         ops.adam(p.t, g.t, m.t, v.t, n, hyper.t, b1, b2, eps, 0.5)
         p3, Mp, m3, Mm, v3, Mv = R.adam(d['p'], d['g'], d['m'], d['acc'], t0, lr, b1, b2, eps, 0.5)
         what = "n = %d t0 = %g" % (n, t0)
-        note('adam_m', m.numpy().ravel(), m3, Mm, R.K_ADAM_M, what)
-        note('adam_v', v.numpy().ravel(), v3, Mv, R.K_ADAM_V, what)
-        note('adam_p', p.numpy().ravel(), p3, Mp, R.K_LIBM['adam_p'], what)
+        note('adam_m', m.numpy().ravel(), m3, Mm, what, k=R.K_ADAM_M)
+        note('adam_v', v.numpy().ravel(), v3, Mv, what, k=R.K_ADAM_V)
+        note('adam_p', p.numpy().ravel(), p3, Mp, what, k=R.K_LIBM['adam_p'])
         assert R.rel(p.numpy().ravel() - d['p'], p3 - d['p']) <= R.REL_L2
         clean(what, p, m, v)
         unchanged(what, g, hyper)
@@ -549,14 +443,14 @@ def test_instance_norm(gpu, mem, row, why):
     yref, M, mu, iv = cached(('in_fwd', shape, group, act), lambda: R.instance_norm_fwd(d['x'], d['gamma'], d['beta'], act, A, group))
     y32, m32, i32 = y.numpy(), mean.numpy().reshape(I, C), inv.numpy().reshape(I, C)
     if act == 'tanh':
-        note('instance_norm_fwd/tanh', y32, yref, M, R.K_LIBM['in_fwd_tanh'], what)
+        note('instance_norm_fwd/tanh', y32, yref, M, what, k=R.K_LIBM['in_fwd_tanh'])
     else:
-        note('instance_norm_fwd', y32, yref, M, R.K_IN_FWD[act], what)
+        note('instance_norm_fwd', y32, yref, M, what, k=R.K_IN_FWD[act])
     # inv's rounding, and the fp64 cancellation E[x^2] - mu^2: two sums of up to 2^17 terms, 2^-36 of E[x^2] at most, which is
     # 2^-12 units of 2^-24
     var = 1 / iv ** 2
-    note('instance_norm_stats', m32, mu, np.abs(mu) + 1e-30, R.K_IN_STATS, what + " mean")
-    note('instance_norm_stats', i32, iv, iv * (1 + 2.0 ** -12 * (mu * mu + var) / var), R.K_IN_STATS, what + " inv")
+    note('instance_norm_stats', m32, mu, np.abs(mu) + 1e-30, what + " mean", k=R.K_IN_STATS)
+    note('instance_norm_stats', i32, iv, iv * (1 + 2.0 ** -12 * (mu * mu + var) / var), what + " inv", k=R.K_IN_STATS)
     plane = y32[:group, C - 1]                                  # the constant instance: var = 0, inv = 1 / sqrt(eps), y = act(beta)
     want = R.Q.restate32_act(d['beta'][C - 1:], act, A)[0] if act != 'tanh' else plane.flat[0]
     exact('instance_norm_fwd', plane, np.full(plane.shape, want, np.float32), what + " constant plane")
@@ -569,13 +463,13 @@ def test_instance_norm(gpu, mem, row, why):
     dg, db = V(gpu, (C,), data=d['prev'][0]), V(gpu, (C,), data=d['prev'][1])
     ops.instance_norm_bwd(dout.t, x.t, dx.t, mean.t, inv.t, gamma.t, beta.t, dg.t, db.t, ws, act, A, accumulate, group)
     ref, Mx, dgr, Mg, dbr, Mb = R.instance_norm_bwd(d['dout'], y32, d['x'], m32, i32, d['gamma'], act, A, group)
-    note('instance_norm_bwd/tanh' if act == 'tanh' else 'instance_norm_bwd', dx.numpy(), ref, Mx,
-         R.K_LIBM['in_bwd_tanh'] if act == 'tanh' else R.K_IN_BWD, what)
+    note('instance_norm_bwd/tanh' if act == 'tanh' else 'instance_norm_bwd', dx.numpy(), ref, Mx, what,
+         k=R.K_LIBM['in_bwd_tanh'] if act == 'tanh' else R.K_IN_BWD)
     prev = d['prev'].astype(np.float64) if accumulate else np.zeros((2, C))
     kg = R.k_in_dgamma(I) + (R.K_LIBM['in_bwd_tanh'] if act == 'tanh' else 0)
     got_g, got_b = dg.numpy().ravel(), db.numpy().ravel()
-    note('instance_norm_dgamma', got_g, dgr + prev[0], Mg + np.abs(prev[0]), kg, what + (" accumulate" if accumulate else ""))
-    note('instance_norm_dbeta', got_b, dbr + prev[1], Mb + np.abs(prev[1]), kg, what + (" accumulate" if accumulate else ""))
+    note('instance_norm_dgamma', got_g, dgr + prev[0], Mg + np.abs(prev[0]), what + (" accumulate" if accumulate else ""), k=kg)
+    note('instance_norm_dbeta', got_b, dbr + prev[1], Mb + np.abs(prev[1]), what + (" accumulate" if accumulate else ""), k=kg)
     clean(what, dx, dg, db)
     unchanged(what, x, dout, gamma, beta, mean, inv)
     if I == 1 and accumulate:           # one instance: fl32(previous + increment) exactly
@@ -615,6 +509,6 @@ def test_axpby_with_b_zero_does_not_read_y(gpu, mem, n):
     prev = y.numpy().ravel()
     ops.axpby(2.0, x.t, -0.5, y.t, n)
     ref = 2.0 * xin.astype(np.float64) - 0.5 * prev
-    note('axpby', y.numpy().ravel(), ref, np.abs(2.0 * xin) + np.abs(0.5 * prev), 3, "n = %d, b = -0.5" % n)
+    note('axpby', y.numpy().ravel(), ref, np.abs(2.0 * xin) + np.abs(0.5 * prev), "n = %d, b = -0.5" % n, k=3)
     clean(n, y)
     unchanged(n, x)

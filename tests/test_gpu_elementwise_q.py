@@ -27,111 +27,24 @@ asserted, and of the rel-L2 (the module prints both when it finishes):
   maxpool2_mask_bwd_q  0.95 of 2                                         5.0e-09
 No entry point needed a fix: all 148 cases passed on their first run.
 """
+import functools
+
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import tuning_env
+from tests import canary
 from tests import elementwise_q_ref as R
 
 pytestmark = pytest.mark.gpu
 
 A = R.ALPHA
-MEASURED = {}
 _REF = {}
-
-
-def cached(key, fn):
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev), device
-    dev.close()
-    _REF.clear()
-    for op in sorted(MEASURED):
-        print("measured %-18s worst k %.3f  rel-L2 %.2e" % ((op,) + MEASURED[op]))
-
-
-@pytest.fixture
-def mem(gpu):
-    """frees what a test allocated"""
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-class F32:
-    """an fp32 tensor whose surroundings hold the canary: a channel slice of a tensor one channel wider on both sides
-    ('slice'), or a contiguous tensor with a tail behind it ('whole')"""
-
-    def __init__(self, gpu, shape, mode, data=None):
-        self.dev, _, D = gpu
-        N, C, H, W = shape
-        HW = H * W
-        if mode == 'slice':
-            self.total, ns, el0 = N * (C + 2) * HW, (C + 2) * HW, HW
-        else:
-            self.total, ns, el0 = N * C * HW + max(HW, 4), C * HW, 0
-        self.ptr = self.dev.alloc(4 * self.total)
-        R.canary_fill(self.dev, self.ptr, 4 * self.total)
-        self.t = D.DevTensor(self.dev, self.ptr + 4 * el0, shape, ns)
-        self.inside = R.f32_inside(N, ns, el0, C * HW, self.total)
-        if data is not None:
-            self.t.set(data)
-
-    def stray(self):
-        return R.canary_changed(self.dev, self.ptr, 4 * self.total, self.inside)
-
-
-class Q:
-    """a q tensor whose surroundings hold the canary: a channel slice in the middle of a buffer 8 channels wider on both sides
-    (piece planes N x nstride apart, as Ops._whole_planes requires), or a whole allocation that ends after its last plane
-    with a tail of one more plane's size behind it"""
-
-    def __init__(self, gpu, shape, dtype, mode):
-        self.dev, _, D = gpu
-        N, C, H, W = shape
-        HW, self.planes = H * W, R.PLANES[dtype]
-        if mode == 'slice':
-            ns, u0 = (C // 8 + 2) * HW, HW
-            self.total = self.planes * N * ns
-        else:
-            ns, u0 = C // 8 * HW, 0
-            self.total = (self.planes + 1) * N * ns
-        self.ptr = self.dev.alloc(16 * self.total)
-        R.canary_fill(self.dev, self.ptr, 16 * self.total)
-        self.q = D.QTensor(self.dev, self.ptr + 16 * u0, shape, dtype, nstride=ns, pstride=N * ns)
-        self.inside = R.q_inside(self.planes, N, ns, N * ns, u0, C // 8 * HW, self.total)
-
-    def stray(self):
-        return R.canary_changed(self.dev, self.ptr, 16 * self.total, self.inside)
-
-    def pieces(self):
-        return [self.q.numpy(piece=p) for p in range(self.planes)]
-
-
-def note(op, got, ref, M, k, what):
-    """assertion 1, with the figures printed before they are asserted and kept for the summary"""
-    w, r = R.worst(got, ref, M), R.rel(got, ref)
-    print("%s %s: worst k %.3f (bound %d)  rel-L2 %.2e" % (op, what, w, k, r))
-    old = MEASURED.get(op, (0.0, 0.0))
-    MEASURED[op] = (max(old[0], w), max(old[1], r))
-    assert np.isfinite(got).all(), (op, what)
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s: element %s got %r ref %r: %.2f x 2^-24 M > k = %d" % (op, what, i, got[i], ref[i], w, k))
-    assert r <= R.REL_L2, (op, what, r)
+LEDGER = canary.Ledger(lambda op, w, r, n: "measured %-18s worst k %.3f  rel-L2 %.2e" % (op, w, r))
+gpu, mem = canary.fixtures(LEDGER, _REF)
+cached = functools.partial(canary.cached, _REF)
+F32, Q = canary.View.framed, canary.QView.framed
+note, clean = LEDGER.note, canary.clean
 
 
 def check_q(gpu, qt, out32, dtype, what):
@@ -165,21 +78,12 @@ def same_planes(a, b, what):
     assert s.size == 0, (what, "%d stray halfwords, first %d" % (s.size, s[0] if s.size else -1))
 
 
-def clean(t, what):
-    s = t.stray()
-    assert s.size == 0, (what, "%d halfwords outside the fp32 view were written, first at element %d" % (s.size, s[0] // 2 if s.size else -1))
-
-
 def vec(dev, a):
     return dev.tensor(np.asarray(a, np.float32))
 
 
 def acts_for(shape, acts):
     return acts if np.prod(shape) <= R.BIG else acts[:1]
-
-
-def accumulated(prev, inc):
-    return (np.asarray(prev, np.float32) + np.asarray(inc, np.float32)).astype(np.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -197,9 +101,9 @@ def test_bn_apply_q(gpu, mem, shape, why, dtype):
         y, q = F32(gpu, shape, 'slice'), Q(gpu, shape, dtype, 'slice')
         ops.bn_apply_q(x.t, y.t, mean, inv, gd, bd, q.q, act, A)
         y32 = y.t.numpy()
-        note('bn_apply_q', y32, ref, M, R.K_BN_APPLY[act], what)
+        note('bn_apply_q', y32, ref, M, what, k=R.K_BN_APPLY[act])
         check_q(gpu, q, y32, dtype, what)
-        clean(y, what)
+        clean(what, y)
         q2 = Q(gpu, shape, dtype, 'whole')
         ops.bn_apply_q(x.t, None, mean, inv, gd, bd, q2.q, act, A)
         same_planes(q, q2, what + " q only")
@@ -208,7 +112,7 @@ def test_bn_apply_q(gpu, mem, shape, why, dtype):
             ops.bn_apply_q(x.t, y3.t, mean, inv, gd, bd, q3.q, act, A)
         assert R.bits_equal(y3.t.numpy(), y32), what + " two pixels"
         same_planes(q, q3, what + " two pixels")
-        clean(y3, what + " two pixels")
+        clean(what + " two pixels", y3)
         for t in (y, q, q2, y3, q3):
             dev.free(t.ptr)
 
@@ -236,9 +140,9 @@ def test_bn_backward_q(gpu, mem, shape, why, dtype):
         dg, db = dev.zeros((1, C, 1, 1)), dev.zeros((1, C, 1, 1))
         ops.bn_backward_q(dout.t, yd.t, x.t, dx.t, mean, inv, gd, dg, db, ws, q.q, act, A)
         dx32 = dx.t.numpy()
-        note('bn_backward_q', dx32, ref, M, R.K_BN_BWD, what)
+        note('bn_backward_q', dx32, ref, M, what, k=R.K_BN_BWD)
         check_q(gpu, q, dx32, dtype, what)
-        clean(dx, what)
+        clean(what, dx)
         inc_g, inc_b = dg.numpy().ravel(), db.numpy().ravel()
         print("%s: dgamma rel-L2 %.2e dbeta rel-L2 %.2e" % (what, R.rel(inc_g, dg_ref), R.rel(inc_b, db_ref)))
         assert R.rel(inc_g, dg_ref) <= R.REL_L2 and R.rel(inc_b, db_ref) <= R.REL_L2, what
@@ -247,21 +151,21 @@ def test_bn_backward_q(gpu, mem, shape, why, dtype):
         dg.set(prev[0]), db.set(prev[1])
         ops.bn_backward_q(dout.t, None, x.t, None, mean, inv, gd, dg, db, ws, q2.q, act, A, accumulate=True, beta=bd)
         same_planes(q, q2, what + " q only, y recomputed")
-        assert R.bits_equal(dg.numpy().ravel(), accumulated(prev[0], inc_g)) and R.bits_equal(db.numpy().ravel(), accumulated(prev[1], inc_b)), what
+        assert R.bits_equal(dg.numpy().ravel(), canary.fl32_sum(prev[0], inc_g)) and R.bits_equal(db.numpy().ravel(), canary.fl32_sum(prev[1], inc_b)), what
         # two pixels per thread
         dx3, q3 = F32(gpu, shape, 'slice'), Q(gpu, shape, dtype, 'slice')
         with tuning_env(GHM_Q_TWO_PIXELS="1"):
             ops.bn_backward_q(dout.t, yd.t, x.t, dx3.t, mean, inv, gd, dg, db, ws, q3.q, act, A)
         dx3_32 = dx3.t.numpy()
-        note('bn_backward_q/px2', dx3_32, ref, M, R.K_BN_BWD, what)
+        note('bn_backward_q/px2', dx3_32, ref, M, what, k=R.K_BN_BWD)
         check_q(gpu, q3, dx3_32, dtype, what + " two pixels")
         same_planes(q, q3, what + " two pixels")
-        clean(dx3, what + " two pixels")
+        clean(what + " two pixels", dx3)
         assert R.bits_equal(dg.numpy().ravel(), inc_g) and R.bits_equal(db.numpy().ravel(), inc_b)
         for t in (yd, dx, q, q2, dx3, q3):
             dev.free(t.ptr)
     for t in (x, dout):
-        clean(t, "inputs")
+        clean("inputs", t)
 
 
 @pytest.mark.parametrize("dtype", R.DTYPES)
@@ -278,9 +182,9 @@ def test_bilinear_and_interleave_q(gpu, mem, shape, why, dtype):
     y, q = F32(gpu, fine, 'whole'), Q(gpu, fine, dtype, 'slice')
     ops.upsample_bilinear2_fwd_q(x.t, y.t, q.q)
     y32 = y.t.numpy()
-    note('bilinear2_fwd_q', y32, ref, M, R.K_BILINEAR, what)
+    note('bilinear2_fwd_q', y32, ref, M, what, k=R.K_BILINEAR)
     check_q(gpu, q, y32, dtype, what)
-    clean(y, what)
+    clean(what, y)
     q2 = Q(gpu, fine, dtype, 'whole')
     ops.upsample_bilinear2_fwd_q(x.t, None, q2.q)
     same_planes(q, q2, what + " q only")
@@ -291,10 +195,10 @@ def test_bilinear_and_interleave_q(gpu, mem, shape, why, dtype):
     ops.pp_to_hi_q(ppd, h.t, hq.q)
     h32 = h.t.numpy()
     hi_ref = R.pp_to_hi(pp)
-    note('pp_to_hi_q', h32, hi_ref.astype(np.float64), np.abs(hi_ref).astype(np.float64), R.K_INTERLEAVE, what)
+    note('pp_to_hi_q', h32, hi_ref.astype(np.float64), np.abs(hi_ref).astype(np.float64), what, k=R.K_INTERLEAVE)
     assert R.bits_equal(h32, hi_ref)
     check_q(gpu, hq, h32, dtype, what + " interleave")
-    clean(h, what + " interleave")
+    clean(what + " interleave", h)
     hq2 = Q(gpu, fine, dtype, 'whole')
     ops.pp_to_hi_q(ppd, None, hq2.q)
     same_planes(hq, hq2, what + " interleave, q only")
@@ -316,16 +220,16 @@ def test_bn_apply_hi(gpu, mem, shape, why, dtype):
         h, q = F32(gpu, fine, 'slice'), Q(gpu, fine, dtype, 'slice')
         ops.bn_apply_hi(ppd, h.t, q.q, mean, inv, gd, bd, act, A)
         h32 = h.t.numpy()
-        note('bn_apply_hi', h32, ref, M, R.K_BN_APPLY[act], what)
+        note('bn_apply_hi', h32, ref, M, what, k=R.K_BN_APPLY[act])
         check_q(gpu, q, h32, dtype, what)
-        clean(h, what)
+        clean(what, h)
         q2 = Q(gpu, fine, dtype, 'whole')
         ops.bn_apply_hi(ppd, None, q2.q, mean, inv, gd, bd, act, A)
         same_planes(q, q2, what + " q only")
         h3 = F32(gpu, fine, 'whole')
         ops.bn_apply_hi(ppd, h3.t, None, mean, inv, gd, bd, act, A)
         assert R.bits_equal(h3.t.numpy(), h32), what + " fp32 only"
-        clean(h3, what + " fp32 only")
+        clean(what + " fp32 only", h3)
         for t in (h, q, q2, h3):
             dev.free(t.ptr)
 
@@ -354,9 +258,9 @@ def test_bn_backward_hi(gpu, mem, shape, why, dtype):
         dg, db = dev.zeros((1, K, 1, 1)), dev.zeros((1, K, 1, 1))
         ops.bn_backward_hi(dhi.t, ppd, dx.t, q.q, mean, inv, gd, bd, dg, db, ws, act, A)
         dx32 = dx.t.numpy()
-        note('bn_backward_hi', dx32, ref, M, R.K_BN_BWD, what)
+        note('bn_backward_hi', dx32, ref, M, what, k=R.K_BN_BWD)
         check_q(gpu, q, dx32, dtype, what)
-        clean(dx, what)
+        clean(what, dx)
         inc_g, inc_b = dg.numpy().ravel(), db.numpy().ravel()
         print("%s: dgamma rel-L2 %.2e dbeta rel-L2 %.2e" % (what, R.rel(inc_g, dg_ref), R.rel(inc_b, db_ref)))
         assert R.rel(inc_g, dg_ref) <= R.REL_L2 and R.rel(inc_b, db_ref) <= R.REL_L2, what
@@ -364,15 +268,15 @@ def test_bn_backward_hi(gpu, mem, shape, why, dtype):
         dg.set(prev[0]), db.set(prev[1])
         ops.bn_backward_hi(dhi.t, ppd, None, q2.q, mean, inv, gd, bd, dg, db, ws, act, A, accumulate=True)
         same_planes(q, q2, what + " q only")
-        assert R.bits_equal(dg.numpy().ravel(), accumulated(prev[0], inc_g)) and R.bits_equal(db.numpy().ravel(), accumulated(prev[1], inc_b)), what
+        assert R.bits_equal(dg.numpy().ravel(), canary.fl32_sum(prev[0], inc_g)) and R.bits_equal(db.numpy().ravel(), canary.fl32_sum(prev[1], inc_b)), what
         dx3 = F32(gpu, ppshape, 'whole')
         ops.bn_backward_hi(dhi.t, ppd, dx3.t, None, mean, inv, gd, bd, dg, db, ws, act, A)
         assert R.bits_equal(dx3.t.numpy(), dx32), what + " fp32 only"
-        clean(dx3, what + " fp32 only")
+        clean(what + " fp32 only", dx3)
         for t in (dx, q, q2, dx3):
             dev.free(t.ptr)
         dev.free(yd.ptr)
-    clean(dhi, "dhi")
+    clean("dhi", dhi)
 
 
 @pytest.mark.parametrize("dtype", R.DTYPES)
@@ -397,9 +301,9 @@ def test_maxpool2_mask_bwd_q(gpu, mem, shape, why, dtype):
             gb = dev.zeros((1, C, 1, 1))
             ops.maxpool2_mask_bwd_q(md, yarg, dypd, dx.t, q.q, act, A, gb)
             dx32 = dx.t.numpy()
-            note('maxpool2_mask_bwd_q', dx32, ref, M, R.K_MASK_BWD, what)
+            note('maxpool2_mask_bwd_q', dx32, ref, M, what, k=R.K_MASK_BWD)
             check_q(gpu, q, dx32, dtype, what)
-            clean(dx, what)
+            clean(what, dx)
             inc = gb.numpy().ravel()
             print("%s: dbias rel-L2 %.2e" % (what, R.rel(inc, db_ref)))
             assert R.rel(inc, db_ref) <= R.REL_L2, what
@@ -408,14 +312,14 @@ def test_maxpool2_mask_bwd_q(gpu, mem, shape, why, dtype):
                 gb.set(prev)
                 ops.maxpool2_mask_bwd_q(md, None, dypd, None, q2.q, act, A, gb, accumulate=True)
                 same_planes(q, q2, what + " q only")
-                assert R.bits_equal(gb.numpy().ravel(), accumulated(prev, inc)), what
+                assert R.bits_equal(gb.numpy().ravel(), canary.fl32_sum(prev, inc)), what
                 dev.free(q2.ptr)
             dx3, q3 = F32(gpu, shape, 'whole'), Q(gpu, shape, dtype, 'slice')
             with tuning_env(GHM_POOLBWD_WINDOWS="1"):
                 ops.maxpool2_mask_bwd_q(md, yarg, dypd, dx3.t, q3.q, act, A, gb)
             assert R.bits_equal(dx3.t.numpy(), dx32), what + " windows"
             same_planes(q, q3, what + " windows")
-            clean(dx3, what + " windows")
+            clean(what + " windows", dx3)
             assert R.rel(gb.numpy().ravel(), db_ref) <= R.REL_L2, what + " windows"
             for t in (dx, q, dx3, q3):
                 dev.free(t.ptr)

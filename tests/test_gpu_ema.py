@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ema_ref
-from tests.test_gpu_resume import NETS, _iterators, assert_same, batches, build, split_run
+from tests.gpu_common import NET_PAIRS as NETS, _iterators, assert_same, batches, build, dev, ops, split_run      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,22 +19,6 @@ POISON = 0xDEADBEEF
 SIZES = [0, 1, 3, 4, 5, 255, 1024, 1027]
 OFFSETS = [4, 64]
 DECAYS = [0.0, 0.5, 0.999]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    d = device.Device(0)
-    yield d
-    d.close()
-
-
-@pytest.fixture(scope="module")
-def ops(dev):
-    from gan_heightmaps_amd.device import Ops
-    return Ops(dev)
 
 
 # ---- kernels ----------------------------------------------------------------------------------------------------------

@@ -11,8 +11,7 @@ from gan_heightmaps_amd._lib import GhmError
 from tests import erosion_ref as R
 from tests import world_ref as WR
 from tests.test_erosion_ref import CASES, F32_DEV, TILE, WIN
-from tests.test_gpu_step import SMALL, build_model
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, dev, ERO, N_WORLD, ops, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -165,8 +164,6 @@ def test_a_window_with_its_halo_equals_the_larger_map_on_the_device(dev, ops):
 
 # ---- 5. the eroded world on SMALL ---------------------------------------------------------------------------------------
 REQ = (-70, 33, 150, 97)                     # 4 x 3 chunks of 64 pixels, both signs
-N_WORLD = 3
-ERO = ER.Erosion(iterations=N_WORLD, **P)
 
 
 @pytest.fixture(scope="module", params=["f32", "bf16x3"])

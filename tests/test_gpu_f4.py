@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests import canary
+
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
@@ -20,14 +22,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev)
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 def _variant(name):
@@ -63,7 +58,7 @@ def _variant(name):
 def test_architecture_variant_on_the_device(gpu, name):
     from tests import lowering_corpus as LC
     from gan_heightmaps_amd import init as INIT, layers as L
-    dev, ops = gpu
+    dev, ops, _ = gpu
     INIT.set_rng(np.random.RandomState(11))
     net, in_layers, feeds = _variant(name)
     if in_layers is None:
@@ -129,7 +124,7 @@ def test_instance_norm_layer_on_the_device(gpu, kind, dtype):
     from oracle import tape as TP
     from gan_heightmaps_amd import init as INIT, layers as L
     from gan_heightmaps_amd.engine import NetPlan, ParamStore
-    dev, ops = gpu
+    dev, ops, _ = gpu
     INIT.set_rng(np.random.RandomState(13))
     net, feeds = _instance_norm_net(kind)
     in_layers = [l for l in L.get_all_layers(net) if isinstance(l, L.InputLayer)]

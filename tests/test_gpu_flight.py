@@ -8,8 +8,7 @@ from oracle import step as ostep
 from gan_heightmaps_amd import render as RN
 from gan_heightmaps_amd import world as WD
 from gan_heightmaps_amd._lib import GhmError
-from tests.test_gpu_step import SMALL, build_model
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, dev, ops, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import step as ostep
+from tests import canary
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev), device
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 HEAVY = [

@@ -9,38 +9,13 @@ from oracle import step as ostep
 from gan_heightmaps_amd import hydrology as HY
 from gan_heightmaps_amd import render as RN
 from tests import hydrology_ref as R
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, CANARY, Canvas, dev, model_params, ops, same, scene_heights, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xAB
 TILE = 32
 PLANES = ('filled', 'flat', 'direction', 'accumulation', 'basin')
 DTYPES = dict(filled=np.float32, flat=np.int32, direction=np.int8, accumulation=np.uint32, basin=np.int32)
-
-
-class Canvas:
-    """an output plane of H x W cells inside a larger buffer of canary bytes -- a row above and below, two cells to the left,
-    the pitch's rest to the right -- in test_gpu_skylight.device_bake's manner"""
-
-    def __init__(self, dev, H, W, dtype, pad=2):
-        self.dev, self.H, self.W, self.dtype = dev, H, W, np.dtype(dtype)
-        self.pitch, self.cell = W + pad, self.dtype.itemsize
-        assert pad >= 2
-        self.whole = np.full((H + 2) * self.pitch * self.cell, CANARY, np.uint8)
-        self.base = dev.alloc(self.whole.nbytes)
-        dev.h2d(self.base, self.whole)
-        self.ptr = self.base + (self.pitch + 2) * self.cell
-
-    def read(self):
-        self.dev.d2h(self.whole, self.base, self.whole.nbytes)
-        grid = self.whole.reshape(self.H + 2, self.pitch * self.cell)
-        body = (slice(1, self.H + 1), slice(2 * self.cell, (2 + self.W) * self.cell))
-        mask = np.ones(grid.shape, bool)
-        mask[body] = False
-        assert (grid[mask] == CANARY).all(), "bytes around the %s plane were written" % self.dtype
-        return np.ascontiguousarray(grid[body]).view(self.dtype).reshape(self.H, self.W).copy()
 
 
 def raw(dev, ops, h, tiled, pad=2, src_pad=0):
@@ -73,13 +48,6 @@ def raw(dev, ops, h, tiled, pad=2, src_pad=0):
             dev.free(b)
     out.update(sweeps=(fill_sweeps, flat_sweeps), rounds=rounds, changed=changed, again=again)
     return out
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype == np.float32:
-        return b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
-    return a.dtype == b.dtype and np.array_equal(a, b)
 
 
 def check_plane(dev, ops, h, label, through_analyse=True):
@@ -251,12 +219,6 @@ def small_model(dev):
     return m
 
 
-def scene_heights(m, hm):
-    """a world's heightmap as a scene maps it: unit range, the mean of three channels"""
-    planes = RN._unit_planes(hm, bool(m.is_a_grayscale), "heightmap")
-    return planes[0] if planes.shape[0] == 1 else planes.astype(np.float64).mean(0).astype(np.float32)
-
-
 def test_model_methods_equal_analyse_and_leave_the_training_state_untouched(small_model, dev, ops):
     m = small_model
     before = model_params(m)
@@ -283,7 +245,7 @@ def test_model_methods_equal_analyse_and_leave_the_training_state_untouched(smal
         # drainage belongs to the rectangle: a sub-rectangle has outlets of its own
         sub = world.hydrology(-10, 20, 30, 40, keep=('accumulation',))
         assert not np.array_equal(sub.accumulation, wh.accumulation[10:40, 10:50])
-    from tests.test_gpu_erosion import ERO
+    from tests.gpu_common import ERO
     with m.terrain_world(42, chunk_cells=2, erosion=ERO) as eroded:              # an eroded world: the eroded heights' drainage
         eh = eroded.hydrology(*rect, keep=('filled',))
         assert same(eh.filled, HY.analyse(ops, scene_heights(m, eroded.heightmap(*rect))).filled)

@@ -29,6 +29,7 @@ import pytest
 from gan_heightmaps_amd import layers as L
 from gan_heightmaps_amd.nonlinearities import LeakyRectify
 from tests import lowering_corpus as LC
+from tests import canary
 
 pytestmark = pytest.mark.gpu
 
@@ -41,14 +42,7 @@ TOL = {          # mode: (output, gradients)
 }
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev)
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 _graphs, _refs = {}, {}
@@ -62,7 +56,7 @@ def _graph_and_reference(name, res):
 
 
 def _run(gpu, name, dtype):
-    dev, ops = gpu
+    dev, ops, _ = gpu
     if name not in _graphs:
         _graphs[name] = LC.graph(name)
     g = _graphs[name]

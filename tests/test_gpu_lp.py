@@ -17,6 +17,8 @@ from gan_heightmaps_amd._lib import tuning_env
 
 from oracle import lp as LP
 from oracle import ops as O
+from tests import canary
+from tests.gpu_common import LP_STEP
 
 pytestmark = pytest.mark.gpu
 
@@ -29,14 +31,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev), device
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 CASES = [
@@ -218,9 +213,6 @@ def test_lp_unsupported_geometries_are_refused(gpu):
 
 
 # ---- the whole train step in reduced precision ---------------------------------------------------------------------
-LP_STEP = dict(in_shp=128, latent_dim=32,
-               gen_dcgan=dict(nch=64, div=[1, 2, 2, 2, 2]), disc_dcgan=dict(nch=64, div=[2, 2, 1, 1]),
-               gen_p2p=dict(nf=16), disc_p2p=dict(nf=32, mul_factor=[1, 2, 4]))
 # Bounds (rel-L2 against the float64 oracle of the same step), ~2x what the MI355X measures (printed by the test):
 #   losses, and the gradients of the BatchNorm-free discriminators: the plain accumulation of operand rounding;
 #   generators: every convolution is followed by a batch-4 BatchNorm whose backward removes the per-channel mean and
@@ -240,7 +232,7 @@ def test_reduced_precision_train_step(gpu, dtype):
     the SAME step, at a size where the 5x5 / 3x3 stride-1, the 3x3 stride-2 (forward, data and weight gradient) and
     the collapsed up-sample convolutions all take the low-precision kernels."""
     from oracle import step as ostep
-    from tests.test_gpu_step import build_model, model_grads, model_params
+    from tests.gpu_common import build_model, model_grads, model_params
     from gan_heightmaps_amd import layers as L
     dev, ops, D = gpu
     cfg = ostep.default_cfg(**LP_STEP)
@@ -296,7 +288,7 @@ def test_reduced_precision_training_follows_the_fp32_trajectory(gpu, dtype):
     the fp32 curves at every step, agree in their last-10-step means, and the reconstruction loss -- the term that
     dominates the U-Net's objective (alpha = 100) -- must fall by the same amount in both runs."""
     from oracle import step as ostep
-    from tests.test_gpu_step import build_model
+    from tests.gpu_common import build_model
     dev, ops, D = gpu
     cfg = ostep.default_cfg(**LP_STEP)
     steps = 40
@@ -332,7 +324,7 @@ def test_fp16_overflow_skips_the_update_and_lowers_the_scale(gpu):
     RMSprop state: the step is skipped on the device (no host round trip: the recorded step replays unchanged), the
     scale is halved, and training resumes by itself once the scale fits."""
     from oracle import step as ostep
-    from tests.test_gpu_step import build_model, model_params, model_grads
+    from tests.gpu_common import build_model, model_params, model_grads
     dev, ops, D = gpu
     cfg = ostep.default_cfg(**LP_STEP)
     model = build_model(cfg, 7, dev, dtype='f16', use_graph='recorded')

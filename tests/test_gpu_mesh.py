@@ -7,25 +7,9 @@ import pytest
 from oracle import step as ostep
 from gan_heightmaps_amd import mesh as MS
 from tests import mesh_ref as M
-from tests.test_gpu_step import SMALL, build_model
+from tests.gpu_common import build_model, dev, ops, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    d = device.Device(0)
-    yield d
-    d.close()
-
-
-@pytest.fixture(scope="module")
-def ops(dev):
-    from gan_heightmaps_amd.device import Ops
-    return Ops(dev)
 
 
 # (seed, rows, cols, k): T = 2, 4, 8 have k <= the fused levels, so the root-diagonal rule applies inside the fused block;
@@ -184,7 +168,7 @@ def test_world_meshes_stitch_bit_for_bit(small_model):
 
 
 def test_an_eroded_world_meshes_as_the_eroded_world(small_model):
-    from tests.test_gpu_erosion import ERO
+    from tests.gpu_common import ERO
     with small_model.terrain_world(42, chunk_cells=2, erosion=ERO) as world, small_model.terrain_world(42, chunk_cells=2) as raw:
         big = _check_world(world, lambda w: w.eroded)
         plain = raw.mesh(-64, 0, 64, 96, max_error=0.01, tile=32)

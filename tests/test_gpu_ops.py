@@ -9,6 +9,7 @@ from gan_heightmaps_amd._lib import tuning_env
 
 from oracle import lp as LP
 from oracle import ops as O
+from tests import canary
 from tests import elementwise_q_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +22,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev), device
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 CONV_CASES = [

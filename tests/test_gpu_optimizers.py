@@ -10,6 +10,7 @@ import pytest
 
 from oracle import ops as O
 from oracle import step as ostep
+from tests.gpu_common import dev      # noqa: F401  (dev: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,16 +77,6 @@ def f32(*xs):
 def rel(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    d = device.Device(0)
-    yield d
-    d.close()
 
 
 # ---- op level ---------------------------------------------------------------------------------------------------------

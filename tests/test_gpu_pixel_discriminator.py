@@ -9,6 +9,7 @@ import pytest
 from oracle import nets as onets
 from oracle import step as ostep
 from oracle import tape as T
+from tests.gpu_common import dev      # noqa: F401  (dev: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,22 +46,12 @@ def pixel_disc(monkeypatch):
     monkeypatch.setattr(onets, "patchgan_fwd", pixel_fwd)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    d = device.Device(0)
-    yield d
-    d.close()
-
-
 @pytest.mark.parametrize("variant", ["lsgan_linear_l1", "bce_sigmoid_l1", "p2p_only_l2"])
 @pytest.mark.parametrize("dtype", ["f32", "bf16x3"])
 def test_train_step_parity_with_the_pixel_discriminator(dev, pixel_disc, variant, dtype):
     """tests/test_gpu_step.py::test_train_step_parity's check with the pixel discriminator: 3 steps (eager, captured +
     launched, graph replay) of losses, gradients and updated parameters against the float64 oracle"""
-    from tests.test_gpu_step import SMALL, build_model, model_grads, model_params, rel
+    from tests.gpu_common import SMALL, build_model, model_grads, model_params, rel
     from gan_heightmaps_amd import layers as L
     over = dict(SMALL, disc_p2p=dict(nf=8, mul_factor=[1, 2]))
     if variant == "bce_sigmoid_l1":
@@ -99,7 +90,7 @@ def test_train_step_parity_with_the_pixel_discriminator(dev, pixel_disc, variant
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16x3"])
 def test_eager_recorded_and_captured_steps_are_bit_identical(dev, pixel_disc, dtype):
-    from tests.test_gpu_step import SMALL, build_model, model_params
+    from tests.gpu_common import SMALL, build_model, model_params
     cfg = ostep.default_cfg(**dict(SMALL, disc_p2p=dict(nf=8, mul_factor=[1, 2])))
     forms = {u: build_model(cfg, 11, dev, use_graph=u, dtype=dtype) for u in (False, 'recorded', True)}
     for it in range(4):
@@ -121,7 +112,7 @@ def test_eager_recorded_and_captured_steps_are_bit_identical(dev, pixel_disc, dt
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16x3"])
 def test_resume_is_bit_identical_with_the_pixel_discriminator(dev, tmp_path, pixel_disc, dtype):
-    from tests.test_gpu_resume import assert_same, split_run
+    from tests.gpu_common import assert_same, split_run
     (la, sa), (lc, sc), _ = split_run('adam', dev, tmp_path, dtype=dtype)
     assert np.array_equal(np.asarray(la), np.asarray(lc))
     assert_same(sa, sc)
@@ -129,7 +120,7 @@ def test_resume_is_bit_identical_with_the_pixel_discriminator(dev, tmp_path, pix
 
 def test_resume_is_bit_identical_through_the_one_rank_sharded_exchange(dev, tmp_path, pixel_disc):
     from gan_heightmaps_amd import device, dist
-    from tests.test_gpu_resume import assert_same, split_run
+    from tests.gpu_common import assert_same, split_run
     cdev = device.Device(dev.index)
     comm = dist.Comm(cdev, 0, 1, channels=(2, 4))
     try:

@@ -41,142 +41,31 @@ the same bits whether the bytes behind them hold NaNs or finite values -- its in
 its flag reads to rows below i_end.  The sizes in include/ghm.h stand as documented; no library source changed.
 """
 import ctypes as C
-import time
 
 import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import GhmError, call, load, tuning_env
-from tests import elementwise_q_ref as Q
+from tests import canary
 from tests import pool_bwd_ref as R
-from tests.test_gpu_conv_s2 import QV, V, clean, unchanged
 
 pytestmark = pytest.mark.gpu
 
-MEASURED = {}
-COUNT = {}
-_T0 = [None]
-GUARD = 4 * R.FRONT                 # bytes of canary in front of and behind every buffer
-PATTERN2 = 0x4248                   # finite as bf16 (50), as fp16 (3.14) and, twice, as fp32 (50.07)
 POOLW_PAIRS = [(4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4), (2, 2)]
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    _T0[0] = time.time()
-    yield dev, device.Ops(dev), device
-    dev.close()
-    for key in sorted(MEASURED):
-        w, r = MEASURED[key]
-        print("measured %-14s worst k %7.3f of %2d  %s %.2e  (%d comparisons)"
-              % (key, w, R.K_BOUND[key.split()[0]], "max-abs/scale" if key.split()[0] in R.MAXABS else "rel-L2", r, COUNT[key]))
-    print("module wall time %.1f s" % (time.time() - _T0[0]))
+def family(key):
+    """'bf16x3 pooled' -> 'bf16x3': the bound and the second figure of a key are those of its first word"""
+    return key.split()[0]
 
 
-@pytest.fixture
-def mem(gpu):
-    dev = gpu[0]
-    before = set(dev._allocs)
-    yield
-    dev.sync()
-    for p in set(dev._allocs) - before:
-        dev.free(p)
-
-
-class Buf:
-    """``nbytes`` of device memory, exactly, between two guards of 4 KB of canary in one allocation"""
-
-    def __init__(self, gpu, nbytes, data=None):
-        self.dev, self.D = gpu[0], gpu[2]
-        self.nbytes = int(nbytes)
-        assert self.nbytes > 0
-        self.total = 2 * GUARD + (self.nbytes + 1) // 2 * 2
-        self.base = self.dev.alloc(self.total)
-        Q.canary_fill(self.dev, self.base, self.total)
-        self.ptr = self.base + GUARD
-        self.inside = np.zeros(self.total // 2, bool)
-        self.inside[GUARD // 2:(GUARD + self.nbytes + 1) // 2] = True
-        self.data = None
-        if data is not None:
-            self.set(data)
-
-    def set(self, data):
-        self.data = np.ascontiguousarray(data).reshape(-1).view(np.uint8).copy()
-        assert self.data.nbytes == self.nbytes, (self.data.nbytes, self.nbytes)
-        self.dev.h2d(self.ptr, self.data)
-        return self
-
-    def bytes(self):
-        out = np.empty(self.nbytes, np.uint8)
-        self.dev.d2h(out, self.ptr, self.nbytes)
-        return out
-
-    def f32(self):
-        return self.bytes().view(np.float32)
-
-    def tensor(self, shape, offset=0):
-        return self.D.DevTensor(self.dev, self.ptr + 4 * offset, shape)
-
-    def stray(self):
-        raw = np.empty(self.total, np.uint8)
-        self.dev.d2h(raw, self.base, self.total)
-        bad = raw != np.full(self.total // 2, Q.CANARY, np.uint16).view(np.uint8)
-        bad[GUARD:GUARD + self.nbytes] = False
-        return np.flatnonzero(bad)
-
-    def same(self):
-        return np.array_equal(self.bytes(), self.data)
-
-    def untouched(self):
-        return np.array_equal(self.bytes(), np.full((self.nbytes + 1) // 2, Q.CANARY, np.uint16).view(np.uint8)[:self.nbytes])
-
-
-def repaint(dev, *objs):
-    """everything outside the views / buffers of these allocations becomes PATTERN2"""
-    for o in objs:
-        base, nbytes = (o.base, o.total) if isinstance(o, Buf) else (o.ptr, 16 * o.total_units if isinstance(o, QV) else 4 * o.total)
-        raw = np.empty(nbytes // 2, np.uint16)
-        dev.d2h(raw, base, nbytes)
-        raw[~o.inside] = PATTERN2
-        dev.h2d(base, raw)
-
-
-def note(key, fam, name, got, ref, M, what):
-    k = R.K_BOUND[fam]
-    got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
-    assert got.shape == ref.shape
-    w = R.worst(got, ref, M)
-    r = float(np.abs(got - ref).max() / np.abs(ref).max()) if fam in R.MAXABS else R.rel(got, ref)
-    print("%s %s %s: worst k %.3f (bound %d)  %.2e" % (key, name, what, w, k, r))
-    old = MEASURED.get(key, (0.0, 0.0))
-    MEASURED[key] = (max(old[0], w), max(old[1], r))
-    COUNT[key] = COUNT.get(key, 0) + 1
-    assert np.isfinite(got).all(), (what, "the output is not finite everywhere: %d elements" % (~np.isfinite(got)).sum())
-    if w > k:
-        err = np.abs(got.astype(np.float64) - ref) / (R.U * np.maximum(M, 1e-300))
-        i = np.unravel_index(np.argmax(np.where(got == ref, 0, err)), got.shape)
-        pytest.fail("%s %s %s: element %s (%s) got %r ref %r: %.2f x 2^-24 M > k = %d"
-                    % (key, name, what, i, R.border_class(name, got.shape, i), got[i], ref[i], w, k))
-    assert r <= (R.MAXABS[fam] if fam in R.MAXABS else R.REL_L2), (what, name, r)
-
-
-def exact(key, name, got, want, what, zero_sign=True):
-    """bit for bit; zero_sign False (relu: v = gp * 0 carries gp's sign): a zero of either sign is a zero"""
-    COUNT[key] = COUNT.get(key, 0) + 1
-    MEASURED.setdefault(key, (0.0, 0.0))
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    if not zero_sign:
-        got, want = np.where(got == 0, np.float32(0), got), np.where(want == 0, np.float32(0), want)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        i = tuple(bad[0])
-        pytest.fail("%s %s %s: %d of %d elements differ in bits, first at %s (%s): got %r, expected %r"
-                    % (key, name, what, len(bad), got.size, i, R.border_class(name, got.shape, i), got[i], want[i]))
+LEDGER = canary.Ledger(lambda key, w, r, n: "measured %-14s worst k %7.3f of %2d  %s %.2e  (%d comparisons)"
+                       % (key, w, R.K_BOUND[family(key)], "max-abs/scale" if family(key) in R.MAXABS else "rel-L2", r, n),
+                       bound=lambda key: R.K_BOUND[family(key)], rel_limit=lambda key: R.MAXABS.get(family(key), R.REL_L2),
+                       maxabs=lambda key: family(key) in R.MAXABS, describe=lambda name, i, shape: R.border_class(name, shape, i))
+gpu, mem = canary.fixtures(LEDGER, {})
+V, Buf, QV = canary.View.named, canary.Bytes, canary.QView.named
+clean, unchanged, repaint, note, exact = canary.clean, canary.unchanged, canary.repaint, LEDGER.note, LEDGER.exact
 
 
 # ---- the sparse fp32 gradients ----
@@ -211,7 +100,7 @@ class Sparse:
         dbb = Buf(self.gpu, 4 * K, self.d['prev_db'] if prev else None)
         ops.conv2d_pool_wgrad_sparse(self.desc, self.x.t, self.mask.ptr, self.yp.tensor(self.sp) if yp else None, self.gp.tensor(self.sp),
                                      dw.ptr, dbb.ptr if db else None, self.ws.ptr, act, alpha, accumulate)
-        return D.unpack_conv_w(dw.f32(), K, 1, 5, 5), (dbb.f32() if db else None), [dw, dbb]
+        return D.unpack_conv_w(dw.numpy(), K, 1, 5, 5), (dbb.numpy() if db else None), [dw, dbb]
 
     def out(self, prev=False, view=None):
         N, H, W, K = self.g
@@ -257,16 +146,16 @@ def test_weight_gradient_row(gpu, mem, case):
             ref = R.ref(d['x'], d['W'], *args_of(d, yp, act, R.SLOPE))
             dW, db, o = p.wgrad(act, R.SLOPE, yp=yp)
             what = "integers, %s, %s" % (act, "yp" if yp else "sign bit")
-            exact(key, 'dW', dW, ref['dW'], what, zero_sign=act != 'relu')
-            exact(key, 'db', db, ref['db'], what, zero_sign=act != 'relu')
+            exact(key, dW, ref['dW'], "dW " + what, at='dW', zero_sign=act != 'relu')
+            exact(key, db, ref['db'], "db " + what, at='db', zero_sign=act != 'relu')
             outs += o
     dW0, _, o = p.wgrad('lrelu', R.SLOPE, db=False)
-    exact(key, 'dW', dW0, ref_of(d, 'lrelu', R.SLOPE)['dW'], "integers, no db")
+    exact(key, dW0, ref_of(d, 'lrelu', R.SLOPE)['dW'], "dW integers, no db", at='dW')
     assert o[1].untouched(), "db was written though none was asked for"
     outs += o
     dW, db, o = p.wgrad('lrelu', R.SLOPE, prev=True, accumulate=True)
-    exact(key, 'dW', dW, d['prev_dW'] + ref_of(d, 'lrelu', R.SLOPE)['dW'], "integers, accumulate")
-    exact(key, 'db', db, d['prev_db'] + ref_of(d, 'lrelu', R.SLOPE)['db'], "integers, accumulate")
+    exact(key, dW, d['prev_dW'] + ref_of(d, 'lrelu', R.SLOPE)['dW'], "dW integers, accumulate", at='dW')
+    exact(key, db, d['prev_db'] + ref_of(d, 'lrelu', R.SLOPE)['db'], "db integers, accumulate", at='db')
     p.settle((case_id(case), "integer pass"), outs + o)
     # ---- real pass ----
     d = sparse_inputs('wgrad', g, False, forward)
@@ -276,28 +165,28 @@ def test_weight_gradient_row(gpu, mem, case):
         a = args_of(d, True, act, R.ALPHA)
         ref, M = R.ref(d['x'], d['W'], *a), R.magnitude(d['x'], d['W'], *a)
         dW, db, o = p.wgrad(act, R.ALPHA)
-        note(key, key, 'dW', dW, ref['dW'], M['dW'], "real, " + act)
-        note(key, key, 'db', db, ref['db'], M['db'], "real, " + act)
+        note(key, dW, ref['dW'], M['dW'], "dW real, " + act, at='dW')
+        note(key, db, ref['db'], M['db'], "db real, " + act, at='db')
         outs += o
         dW2, db2, o = p.wgrad(act, R.ALPHA, yp=False)
-        exact(key, 'dW', dW2, dW, "real, %s: the sign bit gives the bits of yp" % act)
-        exact(key, 'db', db2, db, "real, %s: the sign bit gives the bits of yp" % act)
+        exact(key, dW2, dW, "dW real, %s: the sign bit gives the bits of yp" % act, at='dW')
+        exact(key, db2, db, "db real, %s: the sign bit gives the bits of yp" % act, at='db')
         outs += o
         first = first or (dW, db)
     dW, db = first
     dW2, db2, o = p.wgrad('lrelu', R.ALPHA)
-    exact(key, 'dW', dW2, dW, "real, repeated call")
-    exact(key, 'db', db2, db, "real, repeated call")
+    exact(key, dW2, dW, "dW real, repeated call", at='dW')
+    exact(key, db2, db, "db real, repeated call", at='db')
     outs += o
     dW3, db3, o = p.wgrad('lrelu', R.ALPHA, prev=True, accumulate=True)
-    exact(key, 'dW', dW3, (d['prev_dW'] + dW).astype(np.float32), "real, accumulate == fl32(previous + increment)")
-    exact(key, 'db', db3, (d['prev_db'] + db).astype(np.float32), "real, accumulate == fl32(previous + increment)")
+    exact(key, dW3, (d['prev_dW'] + dW).astype(np.float32), "dW real, accumulate == fl32(previous + increment)", at='dW')
+    exact(key, db3, (d['prev_db'] + db).astype(np.float32), "db real, accumulate == fl32(previous + increment)", at='db')
     outs += o
     p.settle((case_id(case), "real pass"), outs)
     repaint(gpu[0], *p.everything([]))
     dW4, db4, o = p.wgrad('lrelu', R.ALPHA)
-    exact(key, 'dW', dW4, dW, "real, a second pattern outside the views")
-    exact(key, 'db', db4, db, "real, a second pattern outside the views")
+    exact(key, dW4, dW, "dW real, a second pattern outside the views", at='dW')
+    exact(key, db4, db, "db real, a second pattern outside the views", at='db')
 
 
 def ref_of(d, act, alpha, yp=True):
@@ -314,8 +203,8 @@ def test_weight_gradient_launch_shapes_give_the_same_bits(gpu, mem):
         for u, kpw in POOLW_PAIRS:
             with tuning_env(GHM_POOLW_U=str(u), GHM_POOLW_KPW=str(kpw)):
                 dW2, db2, o = p.wgrad('lrelu', R.ALPHA)
-            exact(key, 'dW', dW2, dW, "%s U %d KPW %d" % (R.row_id(row), u, kpw))
-            exact(key, 'db', db2, db, "%s U %d KPW %d" % (R.row_id(row), u, kpw))
+            exact(key, dW2, dW, "dW %s U %d KPW %d" % (R.row_id(row), u, kpw), at='dW')
+            exact(key, db2, db, "db %s U %d KPW %d" % (R.row_id(row), u, kpw), at='db')
             outs += o
         p.settle((R.row_id(row), "launch shapes"), outs)
 
@@ -352,10 +241,11 @@ def test_data_gradient_row(gpu, mem, case):
     for act in R.ACTS:
         for yp in (True, False):
             outs.append(p.out())
-            exact(key, 'dx', p.dgrad(outs[-1], act, R.SLOPE, yp=yp), ref_of(d, act, R.SLOPE, yp)['dx'],
-                  "integers, %s, %s" % (act, "yp" if yp else "sign bit"), zero_sign=act != 'relu')
+            exact(key, p.dgrad(outs[-1], act, R.SLOPE, yp=yp), ref_of(d, act, R.SLOPE, yp)['dx'],
+                  "dx integers, %s, %s" % (act, "yp" if yp else "sign bit"), at='dx', zero_sign=act != 'relu')
     outs.append(p.out(prev=True))
-    exact(key, 'dx', p.dgrad(outs[-1], 'lrelu', R.SLOPE, accumulate=True), d['prev_dx'] + ref_of(d, 'lrelu', R.SLOPE)['dx'], "integers, accumulate")
+    exact(key, p.dgrad(outs[-1], 'lrelu', R.SLOPE, accumulate=True), d['prev_dx'] + ref_of(d, 'lrelu', R.SLOPE)['dx'],
+          "dx integers, accumulate", at='dx')
     if N >= 2:      # one sample of the batch, as the generator's step asks for the fake half
         dev, ops, D = gpu
         o = p.out()
@@ -363,7 +253,7 @@ def test_data_gradient_row(gpu, mem, case):
         ops.conv2d_pool_dgrad_sparse(one, p.mask.ptr + per, p.yp.tensor((1,) + p.sp[1:], per), p.gp.tensor((1,) + p.sp[1:], per), p.w.ptr,
                                      o.t.samples(1, 2), 'lrelu', R.SLOPE)
         got = o.numpy()
-        exact(key, 'dx', got[1:2], ref_of(d, 'lrelu', R.SLOPE)['dx'][1:2], "integers, sample 1 alone")
+        exact(key, got[1:2], ref_of(d, 'lrelu', R.SLOPE)['dx'][1:2], "dx integers, sample 1 alone", at='dx')
         assert np.isnan(got[0]).all() and (N == 2 or np.isnan(got[2:]).all()), "another sample was written"
         outs.append(o)
     p.settle((case_id(case), "integer pass"), outs)
@@ -375,17 +265,17 @@ def test_data_gradient_row(gpu, mem, case):
         ref, M = R.ref(d['x'], d['W'], *a), R.magnitude(d['x'], d['W'], *a)
         outs += [p.out(), p.out()]
         dx = p.dgrad(outs[-2], act, R.ALPHA)
-        note(key, key, 'dx', dx, ref['dx'], M['dx'], "real, " + act)
-        exact(key, 'dx', p.dgrad(outs[-1], act, R.ALPHA, yp=False), dx, "real, %s: the sign bit gives the bits of yp" % act)
+        note(key, dx, ref['dx'], M['dx'], "dx real, " + act, at='dx')
+        exact(key, p.dgrad(outs[-1], act, R.ALPHA, yp=False), dx, "dx real, %s: the sign bit gives the bits of yp" % act, at='dx')
         first = dx if first is None else first
     outs += [p.out(), p.out(prev=True)]
-    exact(key, 'dx', p.dgrad(outs[-2], 'lrelu', R.ALPHA), first, "real, repeated call")
-    exact(key, 'dx', p.dgrad(outs[-1], 'lrelu', R.ALPHA, accumulate=True), (d['prev_dx'] + first).astype(np.float32),
-          "real, accumulate == fl32(previous + increment)")
+    exact(key, p.dgrad(outs[-2], 'lrelu', R.ALPHA), first, "dx real, repeated call", at='dx')
+    exact(key, p.dgrad(outs[-1], 'lrelu', R.ALPHA, accumulate=True), (d['prev_dx'] + first).astype(np.float32),
+          "dx real, accumulate == fl32(previous + increment)", at='dx')
     p.settle((case_id(case), "real pass"), outs)
     o = p.out()
     repaint(gpu[0], *p.everything([o]))
-    exact(key, 'dx', p.dgrad(o, 'lrelu', R.ALPHA), first, "real, a second pattern outside the views")
+    exact(key, p.dgrad(o, 'lrelu', R.ALPHA), first, "dx real, a second pattern outside the views", at='dx')
 
 
 def test_data_gradient_refusals_write_nothing(gpu, mem):
@@ -459,20 +349,20 @@ class Split:
             t.snapshot()
         self.idx.data, self.flags.data = self.idx.bytes(), self.flags.bytes()
         self.produced = [self.dyq, self.cq, self.idx, self.flags]
-        return self.cq.values(), self.idx.bytes().view(np.uint16), self.flags.bytes().view(np.int32)
+        return self.cq.pieces(), self.idx.bytes().view(np.uint16), self.flags.bytes().view(np.int32)
 
     def check_compressed(self, key, act, alpha, yp, what):
         N, Cc, K, H, W = self.g
         cq, idx, flags = self.produce(act, alpha, yp)
         wq, widx, wflags = R.compressed(self.d['mask'], self.d['yp'] if yp else None, self.d['gp'], act, alpha, self.mode)
         for i, (have, want) in enumerate(zip(cq, wq)):
-            exact(key, 'cq', have, want, "%s: cq piece %d" % (what, i), zero_sign=act != 'relu')
+            exact(key, have, want, "cq %s: cq piece %d" % (what, i), at='cq', zero_sign=act != 'relu')
         assert np.array_equal(idx, widx.reshape(-1)), (what, "%d idx words differ" % (idx != widx.reshape(-1)).sum())
         assert np.array_equal(flags, wflags), (what, "flags", flags.reshape(N, H), wflags.reshape(N, H))
         G32 = R.dense_grad(self.d['mask'], self.d['yp'] if yp else None, self.d['gp'], act, alpha, np.float32)
-        exact(key, 'G', self.dense.numpy(), G32, "%s: the dense gradient" % what, zero_sign=act != 'relu')
+        exact(key, self.dense.numpy(), G32, "G %s: the dense gradient" % what, at='G', zero_sign=act != 'relu')
         clean(what, self.dense, *self.produced)
-        COUNT[key] += 2
+        LEDGER.tally(key, 2)
         return G32
 
     def dense_wgrad(self):
@@ -480,14 +370,14 @@ class Split:
         N, Cc, K, H, W = self.g
         o = Buf(self.gpu, 4 * Cc * 25 * K)
         ops.conv2d_wgrad_lp_q(self.desc, self.xq.q, self.dyq.q, o.ptr, self.ws.ptr, self.mode)
-        return D.unpack_conv_w(o.f32(), K, Cc, 5, 5), o
+        return D.unpack_conv_w(o.numpy(), K, Cc, 5, 5), o
 
     def pooled_wgrad(self, prev=None, accumulate=False):
         dev, ops, D = self.gpu
         N, Cc, K, H, W = self.g
         o = Buf(self.gpu, 4 * Cc * 25 * K, None if prev is None else D.pack_conv_w(prev))
         ops.conv2d_wgrad_pooled_split(self.desc, self.xq.q, self.dyq.q, self.cq.q, self.idx.ptr, self.flags.ptr, o.ptr, self.ws.ptr, self.mode, accumulate)
-        return D.unpack_conv_w(o.f32(), K, Cc, 5, 5), o
+        return D.unpack_conv_w(o.numpy(), K, Cc, 5, 5), o
 
     def settle(self, what, outs):
         unchanged(what, *(self.inputs + self.produced))
@@ -516,13 +406,13 @@ def test_compress_and_sparse_instruction_row(gpu, mem, case):
         want = R.wgrad64(d['x'], G32)
         a, oa = p.dense_wgrad()
         b, ob = p.pooled_wgrad()
-        exact(key, 'dW', a, want, "integers: the dense split kernel == float64")
-        exact(key, 'dW', b, want, "integers: the sparse instruction == float64")
+        exact(key, a, want, "dW integers: the dense split kernel == float64", at='dW')
+        exact(key, b, want, "dW integers: the sparse instruction == float64", at='dW')
         with tuning_env(GHM_SPLIT_WGRAD_NO_XCD='1'):
             b2, ob2 = p.pooled_wgrad()
-        exact(key, 'dW', b2, want, "integers, no XCD remap")
+        exact(key, b2, want, "dW integers, no XCD remap", at='dW')
         b3, ob3 = p.pooled_wgrad(prev=d['prev_dW'], accumulate=True)
-        exact(key, 'dW', b3, d['prev_dW'] + want, "integers, accumulate")
+        exact(key, b3, d['prev_dW'] + want, "dW integers, accumulate", at='dW')
         p.settle((case, "integer pass"), [oa, ob, ob2, ob3])
         # ---- real pass ----
         d = R.split_inputs(g, plan, pattern, False)
@@ -531,21 +421,21 @@ def test_compress_and_sparse_instruction_row(gpu, mem, case):
         ref, M = R.ref_split(mode, d['x'], G32), R.wgrad64(np.abs(d['x']), np.abs(G32))
         a, oa = p.dense_wgrad()
         b, ob = p.pooled_wgrad()
-        note(mode + " dense", mode, 'dW', a, ref, M, "real")
-        note(key, mode, 'dW', b, ref, M, "real")
+        note(mode + " dense", a, ref, M, "dW real", at='dW')
+        note(key, b, ref, M, "dW real", at='dW')
         b1, ob1 = p.pooled_wgrad()
-        exact(key, 'dW', b1, b, "real, repeated call")
+        exact(key, b1, b, "dW real, repeated call", at='dW')
         with tuning_env(GHM_SPLIT_WGRAD_NO_XCD='1'):
             b2, ob2 = p.pooled_wgrad()
-        exact(key, 'dW', b2, b, "real, no XCD remap")
+        exact(key, b2, b, "dW real, no XCD remap", at='dW')
         b3, ob3 = p.pooled_wgrad(prev=d['prev_dW'], accumulate=True)
-        exact(key, 'dW', b3, (d['prev_dW'] + b).astype(np.float32), "real, accumulate == fl32(previous + increment)")
+        exact(key, b3, (d['prev_dW'] + b).astype(np.float32), "dW real, accumulate == fl32(previous + increment)", at='dW')
         p.settle((case, "real pass"), [oa, ob, ob1, ob2, ob3])
         # the same bits with another pattern outside every view and buffer: the 256 bytes the older test and the engine add
         # behind idx and flags are not read into a result
         repaint(dev, *(p.inputs + p.produced + [p.ws]))
         b4, ob4 = p.pooled_wgrad()
-        exact(key, 'dW', b4, b, "real, a second pattern outside the views")
+        exact(key, b4, b, "dW real, a second pattern outside the views", at='dW')
 
 
 def test_no_sparse_wgrad_switch_says_no(gpu):

@@ -10,28 +10,13 @@ from gan_heightmaps_amd import hydrology as HY
 from gan_heightmaps_amd import route as RT
 from tests import hydrology_ref as HR
 from tests import route_ref as R
-from tests.test_gpu_hydrology import CANARY, Canvas, same, scene_heights
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, CANARY, Canvas, dev, model_params, ops, padded, same, scene_heights, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
 TILE = 32
 PLANES = ('cost', 'parent', 'territory', 'traffic')
 RAW = dict(cost=np.uint32, parent=np.int8, traffic=np.uint32, basin=np.int32)
-
-
-def padded(dev, plane, dtype, src_pad, fill):
-    """a source plane on the device with a pitch of W + src_pad and ``fill`` beyond its width -> (pointer, pitch)"""
-    if plane is None:
-        return None, 0
-    plane = np.ascontiguousarray(plane, dtype)
-    H, W = plane.shape
-    src = np.full((H, W + src_pad), fill, dtype)
-    src[:, :W] = plane
-    ptr = dev.alloc(src.nbytes)
-    dev.h2d(ptr, src)
-    return ptr, W + src_pad
 
 
 def raw(dev, ops, h, sources, tiled, travel=R.TRAVEL, penalty=None, depth=None, acc=None, pad=2, src_pad=3, resume_with=None):

@@ -13,10 +13,7 @@ from gan_heightmaps_amd import hydrology as HY
 from gan_heightmaps_amd import scatter as SC
 from tests import hydrology_ref as HR
 from tests import scatter_ref as S
-from tests.test_gpu_hydrology import CANARY, Canvas, same
-from tests.test_gpu_route import padded
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, CANARY, Canvas, dev, model_params, ops, padded, same, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 from tests.test_scatter_host import chance_cases
 
 pytestmark = pytest.mark.gpu

@@ -16,8 +16,7 @@ from gan_heightmaps_amd._lib import GhmError
 from tests import erosion_ref
 from tests import render_ref as R
 from tests import skylight_ref as S
-from tests.test_gpu_step import SMALL, build_model
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, dev, ops, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 from tests.test_render_plan import F32_DEV
 from tests.test_skylight_ref import SKY_F32_DEV
 

@@ -14,6 +14,7 @@ import pytest
 from gan_heightmaps_amd._lib import tuning_env
 
 from oracle import ops as O
+from tests import canary
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +26,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-    dev = device.Device(0)
-    yield dev, device.Ops(dev), device
-    dev.close()
+gpu = canary.fixtures()[0]
 
 
 def test_three_bf16_pieces_are_the_fp32_value(gpu):
@@ -360,8 +354,8 @@ def test_split_train_step_meets_the_fp32_bounds(gpu):
     from float64 on the same step + 1e-4 (the full-size tests' formula; a discriminator by its generator's spread as well:
     its gradients inherit the generator's rounding through the fake batch)."""
     from oracle import step as ostep
-    from tests.test_gpu_step import build_model, model_grads, model_params
-    from tests.test_gpu_lp import LP_STEP
+    from tests.gpu_common import build_model, model_grads, model_params
+    from tests.gpu_common import LP_STEP
     from gan_heightmaps_amd import layers as L
     dev, ops, D = gpu
     cfg = ostep.default_cfg(**LP_STEP)

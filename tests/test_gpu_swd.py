@@ -11,8 +11,7 @@ from oracle import step as ostep
 from gan_heightmaps_amd import swd as SW
 from gan_heightmaps_amd.device import DevTensor
 from tests import swd_ref as R
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, dev, model_params, ops, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 

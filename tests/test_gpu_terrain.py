@@ -8,25 +8,9 @@ from oracle import step as ostep
 from gan_heightmaps_amd import terrain as TR
 from gan_heightmaps_amd import util
 from tests import terrain_ref as R
-from tests.test_gpu_step import SMALL, build_model, model_params, rel
+from tests.gpu_common import build_model, dev, model_params, ops, rel, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from gan_heightmaps_amd import device
-    if device.device_count() == 0:
-        pytest.fail("no HIP device visible")
-    d = device.Device(0)
-    yield d
-    d.close()
-
-
-@pytest.fixture(scope="module")
-def ops(dev):
-    from gan_heightmaps_amd.device import Ops
-    return Ops(dev)
 
 
 # ---- 1. seed --------------------------------------------------------------------------------------------------------

@@ -10,10 +10,7 @@ import pytest
 from oracle import step as ostep
 from gan_heightmaps_amd import viewshed as VS
 from tests import viewshed_ref as V
-from tests.test_gpu_hydrology import CANARY, Canvas, same
-from tests.test_gpu_route import padded
-from tests.test_gpu_step import SMALL, build_model, model_params
-from tests.test_gpu_world import dev, ops      # noqa: F401  (the module-scoped fixtures)
+from tests.gpu_common import build_model, CANARY, Canvas, dev, model_params, ops, padded, same, SMALL      # noqa: F401  (dev, ops: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -215,7 +212,7 @@ def test_the_models_methods_and_the_paint(small_model, dev, ops):
 # ---- 4. the world: two rectangles agree where they overlap ------------------------------------------------------------------------
 @pytest.mark.parametrize("eroded", (False, True))
 def test_two_rectangles_of_the_world_agree_bit_for_bit_on_their_overlap(small_model, dev, ops, eroded):
-    from tests.test_gpu_erosion import ERO
+    from tests.gpu_common import ERO
     m = small_model
     kw = dict(erosion=ERO) if eroded else {}
     observers = [(2, 40), (20, 62, 6.0), (10, 75, 1.0, 25.0), (30, 45, None, 300.0)]        # inside both rectangles

@@ -52,12 +52,15 @@ import numpy as np
 import pytest
 
 from gan_heightmaps_amd._lib import GhmError, call
+from tests import canary
 from tests import weight_operand_ref as R
-from tests.test_gpu_elementwise_f32 import gpu, mem  # noqa: F401  (the module-scoped device and the per-test clean-up)
-from tests.test_gpu_elementwise_f32 import V, unchanged, exact, fl32_sum, MEASURED, COUNT
 
 pytestmark = pytest.mark.gpu
 
+_REF = {}
+LEDGER = canary.Ledger(lambda op, w, r, n: "measured %-22s worst k %7.3f  rel-L2 %.2e  (%d comparisons)" % (op, w, r, n))
+gpu, mem = canary.fixtures(LEDGER, _REF, loss_scale=True)
+V, unchanged, fl32_sum, exact = canary.View.free, canary.unchanged, canary.fl32_sum, LEDGER.exact
 DTYPES = R.LP_DTYPES + R.SPLIT_DTYPES
 GAP = 16            # canary bytes between neighbouring destinations of a table
 
@@ -121,8 +124,7 @@ def table_bytes(dev, table, size):
 
 
 def same_halfwords(op, got, want, what):
-    COUNT[op] = COUNT.get(op, 0) + 1
-    MEASURED.setdefault(op, (0.0, 0.0))
+    LEDGER.record(op)
     assert got.shape == want.shape, (op, what, got.shape, want.shape)
     bad = np.flatnonzero(got != want)
     if bad.size:
@@ -136,9 +138,7 @@ def hold_k(op, got, ref, M, k, what):
     got, ref, M = np.asarray(got), np.asarray(ref, np.float64), np.asarray(M, np.float64)
     w, r = R.worst(got, ref, M), R.rel(got, ref)
     print("%s %s: worst k %.3f (bound %d .. %d per element)  rel-L2 %.2e" % (op, what, w, k.min(), k.max(), r))
-    old = MEASURED.get(op, (0.0, 0.0))
-    MEASURED[op] = (max(old[0], w), max(old[1], r))
-    COUNT[op] = COUNT.get(op, 0) + 1
+    LEDGER.record(op, w, r)
     assert np.isfinite(got).all(), (op, what)
     err = np.abs(got.astype(np.float64) - ref)
     bad = err > k * R.U * M
@@ -150,9 +150,6 @@ def hold_k(op, got, ref, M, k, what):
 
 def pack_op(dtype):
     return 'split_pack/' + dtype if dtype in R.SPLIT_DTYPES else 'lp_pack/' + dtype
-
-
-_REF = {}
 
 
 def pack_ref(row, dtype):
@@ -561,8 +558,8 @@ def test_the_operands_the_engine_derives(gpu, mem, dtype):
     -- those BEFORE its update -- because emit_transposes sits between the step's forward and backward passes and the update comes
     last; a forward-only program has no such launch"""
     from oracle import step as ostep
-    from tests.test_gpu_lp import LP_STEP
-    from tests.test_gpu_step import build_model
+    from tests.gpu_common import LP_STEP
+    from tests.gpu_common import build_model
     dev, ops, D = gpu
     cfg = ostep.default_cfg(**LP_STEP)
     model = build_model(cfg, 7, dev, dtype=dtype)
@@ -653,8 +650,7 @@ def test_the_operands_the_engine_derives(gpu, mem, dtype):
             assert not R.bits_equal(e0, e1) and not R.bits_equal(e1, e2), (what, "the weights did not move: the test proves nothing")
             assert not R.bits_equal(got, e0), (what, "still the transform of the INITIAL weights")
             when.add('before' if R.bits_equal(got, e1) else ('after' if R.bits_equal(got, e2) else 'neither'))
-            COUNT['engine transpose'] = COUNT.get('engine transpose', 0) + 1
-            MEASURED.setdefault('engine transpose', (0.0, 0.0))
+            LEDGER.record('engine transpose')
             assert 'neither' not in when, (what, "the transform of no weights this run has had")
     print("engine operands %s: %s; transposed copies hold the weights %s the second step's update" % (dtype, n_items, sorted(when)))
     # every kind the mode has (fp32: no packs; bf16: every master-weight data gradient reads a transposed PACK, only a collapsed
