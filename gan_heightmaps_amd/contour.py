@@ -167,26 +167,49 @@ class Contours:
         return out[np.lexsort(keys + [out["level"]])]
 
     # ---- writers ----------------------------------------------------------------------------------------------------------
-    def save(self, path, texture=None):
+    def save(self, path, texture=None, peaks=None):
         """.npz: the five arrays, origin, shape and the levels; .svg: one <path> per line in pixel coordinates (x = col, y = row),
         index contours in a heavier stroke, Z on the closed ones, ``texture`` (uint8 (H, W) or (H, W, 3)) embedded as a PNG if
         given; .geojson: LineString features with ``level``, ``height``, ``index`` and ``closed`` properties, coordinates
-        [col, row], a closed line repeating its first point"""
+        [col, row], a closed line repeating its first point.  peaks: a peaks.Peaks of the same plane -- the sheet's spot heights:
+        the .svg gains one <circle class="peak"> and one <text> with the height in cells per peak, the .geojson the peaks' Point
+        features; without it both files are what they were"""
         low = path.lower()
+        if peaks is not None:
+            from .peaks import Peaks
+            if not isinstance(peaks, Peaks) or peaks.shape != self.shape or peaks.origin != self.origin:
+                raise ValueError("peaks must be a Peaks of the contours' plane, %d x %d at %r, got %r" % (self.shape + (self.origin, peaks)))
+            if low.endswith(".npz"):
+                raise ValueError("an .npz holds the contours alone: save the peaks on their own")
         if low.endswith(".npz"):
             lv = self.levels
             np.savez(path, edge=self.edge, t=self.t, offsets=self.offsets, level=self.level, closed=self.closed,
                      origin=np.array(self.origin, np.int64), shape=np.array(self.shape, np.int64),
                      levels=np.array([lv.interval, lv.base, -1 if lv.count is None else lv.count, lv.index_every, lv.height_scale]))
         elif low.endswith(".svg"):
+            text = self._svg(texture)
+            if peaks is not None:
+                text = text[:-len("</svg>\n")] + self._svg_peaks(peaks) + "</svg>\n"
             with open(path, "w") as f:
-                f.write(self._svg(texture))
+                f.write(text)
         elif low.endswith(".geojson"):
             import json
+            doc = self._geojson()
+            if peaks is not None:
+                doc["features"] += peaks.features()
             with open(path, "w") as f:
-                json.dump(self._geojson(), f)
+                json.dump(doc, f)
         else:
             raise ValueError("contours are saved as .npz, .svg or .geojson, got %r" % (path,))
+
+    @staticmethod
+    def _svg_peaks(peaks):
+        out = []
+        for (r, c), h in zip(peaks.cell, peaks.height):
+            out.append('<circle class="peak" cx="%d" cy="%d" r="0.8" fill="#4d2e12" stroke="none"/>' % (c, r))
+            out.append('<text class="peak" x="%s" y="%s" font-size="3" fill="#4d2e12" stroke="none">%s</text>' % (
+                repr(int(c) + 1.2), repr(int(r) + 1.0), ("%.1f" % float(h)).rstrip("0").rstrip(".")))
+        return "".join(line + "\n" for line in out)
 
     def _svg(self, texture):
         H, W = self.shape

@@ -1432,6 +1432,63 @@ class Ops:
         call("ghm_contour_marks", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(base_q), int(interval_q), int(count),
              int(index_every), _vp(marks_ptr), int(m_pitch))
 
+    # peaks (csrc/peaks.hip, gan_heightmaps_amd/peaks.py)
+    @staticmethod
+    def peaks_workspace(H, W):
+        """bytes of device workspace peaks_count / peaks_tree / peaks_extract need for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_peaks_workspace(int(H), int(W)))
+
+    @staticmethod
+    def peaks_list_bytes(edges):
+        """bytes of the list buffer the list form of peaks_tree needs for this many edges, or -1"""
+        return int(_lib.load().ghm_peaks_list_bytes(int(edges)))
+
+    def peaks_ascent(self, zq_ptr, z_pitch, H, W, ascent_ptr, a_pitch):
+        """the direction of every cell's neighbour of greatest key (zq, row W + col) if that is above its own, else -1 (a
+        summit) -> the int8 plane at ascent_ptr, in hydrology_accumulate's encoding; asynchronous"""
+        call("ghm_peaks_ascent", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), _vp(ascent_ptr), int(a_pitch))
+
+    def peaks_count(self, zq_ptr, z_pitch, label_ptr, l_pitch, H, W, workspace_ptr):
+        """numbers the summits (label == the cell's own index) and the edges between regions in the workspace.  Returns
+        (summits, edges); waits for the stream"""
+        summits, edges = C.c_int64(0), C.c_int64(0)
+        call("ghm_peaks_count", self.h, _vp(zq_ptr), int(z_pitch), _vp(label_ptr), int(l_pitch), int(H), int(W), _vp(workspace_ptr),
+             C.byref(summits), C.byref(edges))
+        return int(summits.value), int(edges.value)
+
+    def peaks_tree(self, zq_ptr, z_pitch, label_ptr, l_pitch, H, W, form, mask_ptr, m_pitch, workspace_ptr, list_ptr, summits,
+                   edges, max_rounds=32):
+        """the maximum spanning tree of the summits by Boruvka rounds, its edges marked in the uint32 plane at mask_ptr (bit k of
+        cell c); form: 0 plain, 1 list (list_ptr: peaks_list_bytes(edges) bytes; else None).  Returns the rounds; waits for
+        the stream"""
+        rounds = C.c_int32(0)
+        call("ghm_peaks_tree", self.h, _vp(zq_ptr), int(z_pitch), _vp(label_ptr), int(l_pitch), int(H), int(W), int(form),
+             int(max_rounds), _vp(mask_ptr), int(m_pitch), _vp(workspace_ptr), _vp(list_ptr), int(summits), int(edges),
+             C.byref(rounds))
+        return int(rounds.value)
+
+    def peaks_extract(self, label_ptr, l_pitch, area_ptr, a_pitch, mask_ptr, m_pitch, H, W, workspace_ptr, summits, summit_ptr,
+                      area_out_ptr, tree_ptr):
+        """the summits int32 [P] (flat indices, ascending), their areas uint32 [P] and the tree's rows int32 [P - 1, 3] = (cell,
+        its label, the label across) from the workspace of peaks_tree; asynchronous once it has read the totals"""
+        call("ghm_peaks_extract", self.h, _vp(label_ptr), int(l_pitch), _vp(area_ptr), int(a_pitch), _vp(mask_ptr), int(m_pitch),
+             int(H), int(W), _vp(workspace_ptr), int(summits), _vp(summit_ptr), _vp(area_out_ptr), _vp(tree_ptr))
+
+    @staticmethod
+    def peaks_merge(summit, summit_zq, tree, saddle_zq, min_zq):
+        """the host's part (no device): every summit's col (flat index or -1), parent (a summit's number or -1) and prominence
+        in quanta from the extracted summits and tree rows and the heights at both.  Returns (col, parent, prominence_q), int32"""
+        summit, summit_zq = np.ascontiguousarray(summit, np.int32), np.ascontiguousarray(summit_zq, np.int32)
+        tree, saddle_zq = np.ascontiguousarray(tree, np.int32).reshape(-1, 3), np.ascontiguousarray(saddle_zq, np.int32)
+        P, T = summit.shape[0], tree.shape[0]
+        if summit_zq.shape != (P,) or saddle_zq.shape != (T,):
+            raise ValueError("peaks_merge: %d summits with %d heights, %d edges with %d" % (P, summit_zq.size, T, saddle_zq.size))
+        col, parent, prom = np.empty(P, np.int32), np.empty(P, np.int32), np.empty(P, np.int32)
+        _lib.load()
+        call("ghm_peaks_merge", summit.ctypes.data, summit_zq.ctypes.data, P, tree.ctypes.data if T else None,
+             saddle_zq.ctypes.data if T else None, T, int(min_zq), col.ctypes.data, parent.ctypes.data, prom.ctypes.data)
+        return col, parent, prom
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

@@ -372,6 +372,32 @@ class Pix2Pix:
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, heightmap, levels, colour, opacity, index_opacity,
                      value_range=self.is_b_grayscale)
 
+    def heightmap_peaks(self, heightmap, prominence=None, form=None, **kw):
+        """The peaks of a heightmap -- summits with their prominence, key col and parent -- found on the GPU
+        (gan_heightmaps_amd/peaks.py).  Not in the reference.  prominence: a peaks.Prominence (default Prominence():
+        at least 8 cells above the key col); form: 'plain' or 'list', the same bits; kw: peaks.peaks' (origin, max_summits,
+        keep).  Returns a peaks.Peaks.  Intended use:
+
+            found = model.heightmap_peaks(heightmap, Prominence(top=10))
+            seen = model.heightmap_viewshed(heightmap, found.observers(eye_height=10))
+            lines.save("sheet.svg", peaks=found)                                      # the sheet's spot heights
+            painted = model.paint_peaks(texture, found)
+
+        Leaves the training state untouched."""
+        from .peaks import peaks
+        from .step import LANE_OF
+        self.engine.sync()
+        return peaks(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, prominence, form=form, **kw)
+
+    def paint_peaks(self, texture, peaks, colour=(0.9, 0.1, 0.1), radius=2, cols=False):
+        """A texture (this model's generators' or the uint8 paths', of the peaks' plane's size) with a dot of ``radius`` pixels on
+        every peak of a peaks.Peaks -- cols: on every key col -- by the hydrology's paint kernel.  Not in the
+        reference.  Unpainted pixels keep their bits.  Leaves the training state untouched."""
+        from .peaks import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, peaks, colour, radius, cols, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

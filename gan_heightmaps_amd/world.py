@@ -36,6 +36,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--routes OUT_PREFIX --from Y,X [--from Y,X ...] [--to Y,X ...]] [--earthworks OUT] [--scatter OUT --spacing X]
         [--viewshed OUT --from Y,X [--from Y,X ...]]
         [--contours OUT.{svg,geojson,npz} [--interval X] [--base X] [--count N] [--index-every N]]
+        [--peaks OUT.{geojson,csv,npz} [--min-prominence X] [--top N]]
 """
 import argparse
 import collections
@@ -783,6 +784,18 @@ class TerrainWorld:
         hm = self._unit_height(y0, x0, h, w)
         return contours(self._ops, hm, levels, origin=(y0, x0))
 
+    def peaks(self, y0, x0, h, w, prominence=None):
+        """the peaks of ``self.heightmap(y0, x0, h, w)`` (peaks.Peaks), heights mapped as a scene's; a plain or an
+        eroded world.  prominence: a peaks.Prominence; the Peaks' ``origin`` is (y0, x0), its ``cell`` and ``col`` are in world
+        coordinates.
+        Peaks belong to the rectangle, like drainage and routes: a mountain the edge cuts is ranked by what is inside (``on_edge``
+        marks the summits on the border), ties between equal heights are broken by the rectangle's own cell order, and two
+        rectangles do NOT agree where they overlap.  Nothing is cached."""
+        from .peaks import peaks
+        y0, x0 = int(y0), int(x0)
+        hm = self._unit_height(y0, x0, h, w)
+        return peaks(self._ops, hm, prominence, origin=(y0, x0))
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -984,6 +997,11 @@ def parse_args(argv):
                         ".npz; --interval, --base, --count and --index-every choose the levels")
     from . import contour as _contour
     _contour.add_level_arguments(p)
+    p.add_argument("--peaks", default=None, metavar="OUT",
+                   help="also write the region's peaks in world coordinates (peaks' height scale): .geojson, .csv or .npz; "
+                        "--min-prominence and --top choose them; with --contours OUT.svg the sheet gets their spot heights")
+    from . import peaks as _peaks
+    _peaks.add_prominence_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
@@ -1015,6 +1033,16 @@ def parse_args(argv):
             p.error("--contours writes .svg, .geojson or .npz")
         try:
             a.levels = _contour.Levels(*chosen)
+        except ValueError as e:
+            p.error(str(e))
+    if a.peaks is None:
+        if (a.min_prominence, a.top) != (_peaks.Prominence().min_prominence, None):
+            p.error("--min-prominence / --top need --peaks")
+    else:
+        if not a.peaks.lower().endswith((".geojson", ".csv", ".npz")):
+            p.error("--peaks writes .geojson, .csv or .npz")
+        try:
+            a.prominence = _peaks.Prominence(a.min_prominence, a.top)
         except ValueError as e:
             p.error(str(e))
     if (a.scatter is None) != (a.spacing is None):
@@ -1090,8 +1118,13 @@ def main(argv=None):
             world.scatter(y0, x0, h, w, a.species).save(a.scatter)
         if a.viewshed:
             world.viewshed(y0, x0, h, w, a.sources).save(a.viewshed)
+        found = None
+        if a.peaks:
+            found = world.peaks(y0, x0, h, w, a.prominence)
+            found.save(a.peaks)
         if a.contours:
-            world.contours(y0, x0, h, w, a.levels).save(a.contours)
+            spot = found if a.contours.lower().endswith(".svg") else None
+            world.contours(y0, x0, h, w, a.levels).save(a.contours, peaks=spot)
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
