@@ -224,6 +224,10 @@ SIGNATURES = {
     "ghm_peaks_tree": [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _i64, _i64, C.POINTER(_i32)],
     "ghm_peaks_extract": [_p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _p, _p],
     "ghm_peaks_merge": [_p, _p, _i64, _p, _p, _i64, _i32, _p, _p, _p],
+    "ghm_rivers_count": [_p, _p, _i32, _p, _i32, _i32, _i32, C.c_uint32, _p, _i32, _p, C.POINTER(_i64)],
+    "ghm_rivers_trace": [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _i64, C.POINTER(_i64), C.POINTER(_i32)],
+    "ghm_rivers_extract": [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _i64, _i64, _i64, _p, _p, _p],
+    "ghm_rivers_order": [_p, _p, _i64, _p, _p, _p],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -285,6 +289,8 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_contour_workspace": ([_i32, _i32, _i64], C.c_int64),
             "ghm_peaks_workspace": ([_i32, _i32], C.c_int64),
             "ghm_peaks_list_bytes": ([_i64], C.c_int64),
+            "ghm_rivers_workspace": ([_i32, _i32], C.c_int64),
+            "ghm_rivers_list_bytes": ([_i64], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

@@ -167,14 +167,22 @@ class Contours:
         return out[np.lexsort(keys + [out["level"]])]
 
     # ---- writers ----------------------------------------------------------------------------------------------------------
-    def save(self, path, texture=None, peaks=None):
+    def save(self, path, texture=None, peaks=None, rivers=None):
         """.npz: the five arrays, origin, shape and the levels; .svg: one <path> per line in pixel coordinates (x = col, y = row),
         index contours in a heavier stroke, Z on the closed ones, ``texture`` (uint8 (H, W) or (H, W, 3)) embedded as a PNG if
         given; .geojson: LineString features with ``level``, ``height``, ``index`` and ``closed`` properties, coordinates
         [col, row], a closed line repeating its first point.  peaks: a peaks.Peaks of the same plane -- the sheet's spot heights:
         the .svg gains one <circle class="peak"> and one <text> with the height in cells per peak, the .geojson the peaks' Point
-        features; without it both files are what they were"""
+        features; without it both files are what they were.  rivers: a rivers.Rivers of the same plane -- the sheet's blue lines:
+        the .svg gains one <path class="river"> per reach before the peaks' marks, the .geojson the reaches' LineString features
+        after the contours' and before the peaks'; without it both files are what they were"""
         low = path.lower()
+        if rivers is not None:
+            from .rivers import Rivers
+            if not isinstance(rivers, Rivers) or rivers.shape != self.shape or rivers.origin != self.origin:
+                raise ValueError("rivers must be a Rivers of the contours' plane, %d x %d at %r, got %r" % (self.shape + (self.origin, rivers)))
+            if low.endswith(".npz"):
+                raise ValueError("an .npz holds the contours alone: save the rivers on their own")
         if peaks is not None:
             from .peaks import Peaks
             if not isinstance(peaks, Peaks) or peaks.shape != self.shape or peaks.origin != self.origin:
@@ -188,6 +196,8 @@ class Contours:
                      levels=np.array([lv.interval, lv.base, -1 if lv.count is None else lv.count, lv.index_every, lv.height_scale]))
         elif low.endswith(".svg"):
             text = self._svg(texture)
+            if rivers is not None:
+                text = text[:-len("</svg>\n")] + rivers._svg_paths() + "</svg>\n"
             if peaks is not None:
                 text = text[:-len("</svg>\n")] + self._svg_peaks(peaks) + "</svg>\n"
             with open(path, "w") as f:
@@ -195,6 +205,8 @@ class Contours:
         elif low.endswith(".geojson"):
             import json
             doc = self._geojson()
+            if rivers is not None:
+                doc["features"] += rivers.features()
             if peaks is not None:
                 doc["features"] += peaks.features()
             with open(path, "w") as f:

@@ -1489,6 +1489,56 @@ class Ops:
              saddle_zq.ctypes.data if T else None, T, int(min_zq), col.ctypes.data, parent.ctypes.data, prom.ctypes.data)
         return col, parent, prom
 
+    # rivers (csrc/rivers.hip, gan_heightmaps_amd/rivers.py)
+    @staticmethod
+    def rivers_workspace(H, W):
+        """bytes of device workspace rivers_count / rivers_trace / rivers_extract need for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_rivers_workspace(int(H), int(W)))
+
+    @staticmethod
+    def rivers_list_bytes(cells):
+        """bytes of the list buffer the list form of rivers_trace needs for this many stream cells, or -1"""
+        return int(_lib.load().ghm_rivers_list_bytes(int(cells)))
+
+    def rivers_count(self, dir_ptr, d_pitch, acc_ptr, a_pitch, H, W, threshold, kind_ptr, k_pitch, workspace_ptr):
+        """the stream cells (accumulation >= threshold) of the int8 direction and uint32 accumulation planes: their kind -> the
+        uint8 plane at kind_ptr, the reach starts and the stream cells numbered in the workspace.  Returns (cells, reaches,
+        sources, confluences, mouths, isolated); waits for the stream"""
+        counts = (C.c_int64 * 6)()
+        call("ghm_rivers_count", self.h, _vp(dir_ptr), int(d_pitch), _vp(acc_ptr), int(a_pitch), int(H), int(W), int(threshold),
+             _vp(kind_ptr), int(k_pitch), _vp(workspace_ptr), counts)
+        return tuple(int(v) for v in counts)
+
+    def rivers_trace(self, dir_ptr, d_pitch, kind_ptr, k_pitch, H, W, form, workspace_ptr, list_ptr, cells, reaches, max_rounds=32):
+        """ranks the cells along their reaches by pointer doubling and stores every reach's length and downstream reach in the
+        workspace; form: 0 plain, 1 list (list_ptr: rivers_list_bytes(cells) bytes; else None).  Returns (vertices, the rounds
+        that moved a pointer); waits for the stream"""
+        vertices, rounds = C.c_int64(0), C.c_int32(0)
+        call("ghm_rivers_trace", self.h, _vp(dir_ptr), int(d_pitch), _vp(kind_ptr), int(k_pitch), int(H), int(W), int(form),
+             int(max_rounds), _vp(workspace_ptr), _vp(list_ptr), int(cells), int(reaches), C.byref(vertices), C.byref(rounds))
+        return int(vertices.value), int(rounds.value)
+
+    def rivers_extract(self, dir_ptr, d_pitch, kind_ptr, k_pitch, H, W, workspace_ptr, list_ptr, cells, reaches, vertices, vertex_ptr,
+                       offsets_ptr, downstream_ptr):
+        """the traced reaches -> vertex int32 [V] (flat indices, reach by reach, downstream), offsets int64 [R + 1], downstream
+        int32 [R]; the totals are rivers_count's and rivers_trace's; asynchronous once it has compared them with the workspace's"""
+        call("ghm_rivers_extract", self.h, _vp(dir_ptr), int(d_pitch), _vp(kind_ptr), int(k_pitch), int(H), int(W), _vp(workspace_ptr),
+             _vp(list_ptr), int(cells), int(reaches), int(vertices), _vp(vertex_ptr), _vp(offsets_ptr), _vp(downstream_ptr))
+
+    @staticmethod
+    def rivers_order(downstream, area):
+        """the host's part (no device): every reach's Strahler order, Shreve magnitude (int32 each) and whether it is the main
+        stem where it ends (uint8), from the reaches' downstream reach (or -1) and their areas.  Returns (order, magnitude, main)"""
+        downstream, area = np.ascontiguousarray(downstream, np.int32), np.ascontiguousarray(area, np.uint32)
+        R = downstream.shape[0]
+        if downstream.ndim != 1 or area.shape != (R,):
+            raise ValueError("rivers_order: %d reaches with %d areas" % (downstream.size, area.size))
+        order, magnitude, main = np.empty(R, np.int32), np.empty(R, np.int32), np.empty(R, np.uint8)
+        _lib.load()
+        call("ghm_rivers_order", downstream.ctypes.data if R else None, area.ctypes.data if R else None, R,
+             order.ctypes.data if R else None, magnitude.ctypes.data if R else None, main.ctypes.data if R else None)
+        return order, magnitude, main
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

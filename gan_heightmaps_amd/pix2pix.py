@@ -398,6 +398,42 @@ class Pix2Pix:
         self.engine.sync()
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, peaks, colour, radius, cols, value_range=self.is_b_grayscale)
 
+    def heightmap_rivers(self, heightmap_or_hydrology, network=None, form=None, **kw):
+        """The rivers of a heightmap -- the stream network as ordered reaches with their Strahler orders, Shreve magnitudes and
+        main stems -- traced on the GPU (gan_heightmaps_amd/rivers.py).  Not in the reference.
+        heightmap_or_hydrology: a heightmap as ``heightmap_hydrology`` takes it, which is analysed first, or a
+        hydrology.Hydrology that kept 'direction' and 'accumulation'; network: a rivers.Network (default Network(): a stream
+        from 256 cells of drainage area on); form: 'plain' or 'list', the same bits; kw: rivers.rivers' (origin, max_reaches,
+        keep).  Returns a rivers.Rivers.  Intended use:
+
+            found = model.heightmap_rivers(heightmap, Network(min_order=2))
+            lines.save("sheet.svg", peaks=tops, rivers=found)                         # the sheet's blue lines
+            roads = model.heightmap_routes(heightmap, found.confluences())            # towns where rivers meet
+            painted = model.paint_rivers(texture, found)
+
+        Leaves the training state untouched."""
+        from .hydrology import Hydrology, analyse
+        from .rivers import rivers
+        from .step import LANE_OF
+        self.engine.sync()
+        ops = self.engine.ops[LANE_OF['dcgan_gen']]
+        hydro = heightmap_or_hydrology
+        if not isinstance(hydro, Hydrology):
+            hydro = analyse(ops, hydro, keep=('filled', 'depth', 'direction', 'accumulation'))
+        return rivers(ops, hydro, network, form=form, **kw)
+
+    def paint_rivers(self, texture, rivers, min_order=1, width=0, colour=None, opacity=0.85):
+        """A texture (this model's generators' or the uint8 paths', of the rivers' plane's size) with the reaches of a
+        rivers.Rivers of at least ``min_order`` drawn ``width`` pixels (0 .. 4) to either side by the hydrology's paint kernel
+        (DESIGN §4za); colour: default the water's.  Not in the reference.  Unpainted pixels keep their bits.  Leaves the
+        training state untouched."""
+        from .hydrology import Water
+        from .rivers import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, rivers, min_order, width, Water().colour if colour is None else colour,
+                     opacity, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

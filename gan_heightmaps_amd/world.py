@@ -37,6 +37,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--viewshed OUT --from Y,X [--from Y,X ...]]
         [--contours OUT.{svg,geojson,npz} [--interval X] [--base X] [--count N] [--index-every N]]
         [--peaks OUT.{geojson,csv,npz} [--min-prominence X] [--top N]]
+        [--rivers OUT.{svg,geojson,npz} [--river-threshold N] [--min-order N]]
 """
 import argparse
 import collections
@@ -796,6 +797,18 @@ class TerrainWorld:
         hm = self._unit_height(y0, x0, h, w)
         return peaks(self._ops, hm, prominence, origin=(y0, x0))
 
+    def rivers(self, y0, x0, h, w, network=None):
+        """the rivers of ``self.heightmap(y0, x0, h, w)`` (rivers.Rivers): ``self.hydrology`` of the rectangle, then
+        its stream network; a plain or an eroded world.  network: a rivers.Network; the Rivers' ``origin`` is (y0, x0) and its
+        ``points`` are in world coordinates.
+        Rivers belong to the rectangle, like the drainage they are built on: its edge is the outlet, areas count cells of the
+        rectangle alone, so orders and main stems are the rectangle's and two rectangles do NOT agree where they overlap.
+        Nothing is cached and no seam is handled."""
+        from .rivers import rivers
+        y0, x0 = int(y0), int(x0)
+        hydro = self.hydrology(y0, x0, h, w, keep=('filled', 'depth', 'direction', 'accumulation'))
+        return rivers(self._ops, hydro, network, origin=(y0, x0))
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -1002,6 +1015,12 @@ def parse_args(argv):
                         "--min-prominence and --top choose them; with --contours OUT.svg the sheet gets their spot heights")
     from . import peaks as _peaks
     _peaks.add_prominence_arguments(p)
+    p.add_argument("--rivers", default=None, metavar="OUT",
+                   help="also write the region's rivers in world coordinates, ordered reaches with their Strahler orders: .svg, "
+                        ".geojson or .npz; --river-threshold and --min-order choose them; with --contours OUT.svg or OUT.geojson "
+                        "the sheet gets their blue lines")
+    from . import rivers as _rivers
+    _rivers.add_network_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
@@ -1043,6 +1062,16 @@ def parse_args(argv):
             p.error("--peaks writes .geojson, .csv or .npz")
         try:
             a.prominence = _peaks.Prominence(a.min_prominence, a.top)
+        except ValueError as e:
+            p.error(str(e))
+    if a.rivers is None:
+        if (a.river_threshold, a.min_order) != (_rivers.Network().river_threshold, _rivers.Network().min_order):
+            p.error("--river-threshold / --min-order need --rivers")
+    else:
+        if not a.rivers.lower().endswith((".svg", ".geojson", ".npz")):
+            p.error("--rivers writes .svg, .geojson or .npz")
+        try:
+            a.network = _rivers.Network(a.river_threshold, a.min_order)
         except ValueError as e:
             p.error(str(e))
     if (a.scatter is None) != (a.spacing is None):
@@ -1122,9 +1151,14 @@ def main(argv=None):
         if a.peaks:
             found = world.peaks(y0, x0, h, w, a.prominence)
             found.save(a.peaks)
+        blue = None
+        if a.rivers:
+            blue = world.rivers(y0, x0, h, w, a.network)
+            blue.save(a.rivers)
         if a.contours:
             spot = found if a.contours.lower().endswith(".svg") else None
-            world.contours(y0, x0, h, w, a.levels).save(a.contours, peaks=spot)
+            world.contours(y0, x0, h, w, a.levels).save(a.contours, peaks=spot,
+                                                        rivers=None if a.contours.lower().endswith(".npz") else blue)
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
