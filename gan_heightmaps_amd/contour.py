@@ -167,7 +167,7 @@ class Contours:
         return out[np.lexsort(keys + [out["level"]])]
 
     # ---- writers ----------------------------------------------------------------------------------------------------------
-    def save(self, path, texture=None, peaks=None, rivers=None):
+    def save(self, path, texture=None, peaks=None, rivers=None, regions=None):
         """.npz: the five arrays, origin, shape and the levels; .svg: one <path> per line in pixel coordinates (x = col, y = row),
         index contours in a heavier stroke, Z on the closed ones, ``texture`` (uint8 (H, W) or (H, W, 3)) embedded as a PNG if
         given; .geojson: LineString features with ``level``, ``height``, ``index`` and ``closed`` properties, coordinates
@@ -175,8 +175,17 @@ class Contours:
         the .svg gains one <circle class="peak"> and one <text> with the height in cells per peak, the .geojson the peaks' Point
         features; without it both files are what they were.  rivers: a rivers.Rivers of the same plane -- the sheet's blue lines:
         the .svg gains one <path class="river"> per reach before the peaks' marks, the .geojson the reaches' LineString features
-        after the contours' and before the peaks'; without it both files are what they were"""
+        after the contours' and before the peaks'; without it both files are what they were.  regions: a regions.Regions of the
+        same plane -- the sheet's filled areas: the .svg gains one even-odd <path class="region"> per polygon beneath the lines
+        (after the texture, before the first line), the .geojson the polygons' Polygon features in front of the contours';
+        without it both files are what they were"""
         low = path.lower()
+        if regions is not None:
+            from .regions import Regions
+            if not isinstance(regions, Regions) or regions.shape != self.shape or regions.origin != self.origin:
+                raise ValueError("regions must be a Regions of the contours' plane, %d x %d at %r, got %r" % (self.shape + (self.origin, regions)))
+            if low.endswith(".npz"):
+                raise ValueError("an .npz holds the contours alone: save the regions on their own")
         if rivers is not None:
             from .rivers import Rivers
             if not isinstance(rivers, Rivers) or rivers.shape != self.shape or rivers.origin != self.origin:
@@ -196,6 +205,10 @@ class Contours:
                      levels=np.array([lv.interval, lv.base, -1 if lv.count is None else lv.count, lv.index_every, lv.height_scale]))
         elif low.endswith(".svg"):
             text = self._svg(texture)
+            if regions is not None:
+                # a cell's centre is its position on the sheet, so its corners lie half a cell before it
+                at = text.index("\n", text.index("<image") if texture is not None else 0) + 1
+                text = text[:at] + '<g transform="translate(-0.5 -0.5)">\n' + regions._svg_paths() + "</g>\n" + text[at:]
             if rivers is not None:
                 text = text[:-len("</svg>\n")] + rivers._svg_paths() + "</svg>\n"
             if peaks is not None:
@@ -205,6 +218,8 @@ class Contours:
         elif low.endswith(".geojson"):
             import json
             doc = self._geojson()
+            if regions is not None:
+                doc["features"] = regions.features() + doc["features"]
             if rivers is not None:
                 doc["features"] += rivers.features()
             if peaks is not None:

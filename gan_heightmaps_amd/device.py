@@ -1539,6 +1539,55 @@ class Ops:
              order.ctypes.data if R else None, magnitude.ctypes.data if R else None, main.ctypes.data if R else None)
         return order, magnitude, main
 
+    # regions (csrc/regions.hip, gan_heightmaps_amd/regions.py)
+    @staticmethod
+    def regions_workspace(H, W):
+        """bytes of device workspace regions_label / _count / _trace / _extract need for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_regions_workspace(int(H), int(W)))
+
+    @staticmethod
+    def regions_trace_bytes(edges):
+        """bytes of the per-edge buffers regions_trace needs for this many boundary edges, or -1"""
+        return int(_lib.load().ghm_regions_trace_bytes(int(edges)))
+
+    def regions_label(self, labels_ptr, l_pitch, H, W, form, component_ptr, c_pitch, workspace_ptr):
+        """the int32 label plane (negative: no region) -> the int32 component plane: the least flat index of every cell's
+        4-connected component of equal labels, -1 for none; form: 0 sweep, 1 union, the same bits.  Returns the sweeps issued, 0
+        if no cell has a region; waits for the stream"""
+        sweeps = C.c_int64(0)
+        call("ghm_regions_label", self.h, _vp(labels_ptr), int(l_pitch), int(H), int(W), int(form), _vp(component_ptr), int(c_pitch),
+             _vp(workspace_ptr), C.byref(sweeps))
+        return int(sweeps.value)
+
+    def regions_count(self, labels_ptr, l_pitch, component_ptr, c_pitch, H, W, workspace_ptr, max_edges=(1 << 31) - 1):
+        """numbers the boundary edges and the polygons of a labelled plane in the workspace and counts the polygons' cells; more
+        than max_edges edges are refused.  Returns (edges, polygons); waits for the stream"""
+        counts = (C.c_int64 * 2)()
+        call("ghm_regions_count", self.h, _vp(labels_ptr), int(l_pitch), _vp(component_ptr), int(c_pitch), int(H), int(W),
+             int(max_edges), _vp(workspace_ptr), counts)
+        return int(counts[0]), int(counts[1])
+
+    def regions_trace(self, H, W, workspace_ptr, trace_ptr, edges, polygons, max_rounds=32):
+        """links the counted edges into rings, finds every ring's least edge and ranks the edges with their corner counts by
+        pointer doubling, in the buffer at trace_ptr (regions_trace_bytes(edges) bytes).  Returns (rings, vertices, the ranking's
+        rounds that moved a pointer); waits for the stream"""
+        counts, rounds = (C.c_int64 * 2)(), C.c_int32(0)
+        call("ghm_regions_trace", self.h, int(H), int(W), int(max_rounds), _vp(workspace_ptr), _vp(trace_ptr), int(edges), int(polygons),
+             counts, C.byref(rounds))
+        return int(counts[0]), int(counts[1]), int(rounds.value)
+
+    def regions_extract(self, labels_ptr, l_pitch, component_ptr, c_pitch, H, W, workspace_ptr, trace_ptr, edges, polygons, rings,
+                        vertices, vertex_ptr, ring_offsets_ptr, ring_polygon_ptr, ring_hole_ptr, seed_ptr, label_ptr, cells_ptr,
+                        polygon_ptr=None, p_pitch=0):
+        """the traced rings -> vertex int32 [V] (grid corners row (W + 1) + col), ring_offsets int64 [R + 1], ring_polygon int32
+        [R], ring_hole uint8 [R], seed and label int32 [P], cells uint32 [P] and, if polygon_ptr is given, the polygon of every
+        cell, int32 in rows of p_pitch cells; the totals are regions_count's and regions_trace's; asynchronous once it has
+        compared them with the workspace's"""
+        call("ghm_regions_extract", self.h, _vp(labels_ptr), int(l_pitch), _vp(component_ptr), int(c_pitch), int(H), int(W),
+             _vp(workspace_ptr), _vp(trace_ptr), int(edges), int(polygons), int(rings), int(vertices), _vp(vertex_ptr),
+             _vp(ring_offsets_ptr), _vp(ring_polygon_ptr), _vp(ring_hole_ptr), _vp(seed_ptr), _vp(label_ptr), _vp(cells_ptr),
+             _vp(polygon_ptr), int(p_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

@@ -434,6 +434,54 @@ class Pix2Pix:
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, rivers, min_order, width, Water().colour if colour is None else colour,
                      opacity, value_range=self.is_b_grayscale)
 
+    def heightmap_regions(self, labels_or_heightmap, of='lakes', areas=None, form=None, **kw):
+        """The areas of a heightmap or of a label plane as polygons with holes -- an outer ring and its islands, in order, with
+        the number of cells -- labelled and traced on the GPU (gan_heightmaps_amd/regions.py).  Not in the reference.
+        labels_or_heightmap: an integer plane (H, W) is a label plane (negative: no region) and ``of`` is not read; a heightmap
+        as ``heightmap_hydrology`` takes it is turned into one first: of='lakes' or 'basins' through its hydrology, 'land'
+        (kw sea_level, a number in [0, 1]) or 'bands' (kw levels, a contour.Levels).  areas: a regions.Areas; form: 'sweep' or
+        'union', the same bits; kw besides: regions.regions' (origin, keep, max_edges).  Returns a regions.Regions.  Intended use:
+
+            water = model.heightmap_regions(heightmap, 'lakes', Areas(min_cells=16))
+            water.save("lakes.geojson")
+            lines.save("sheet.svg", regions=water)                                    # the sheet's filled lakes
+            painted = model.paint_regions(texture, water, (0.2, 0.4, 0.8), 0.6)
+
+        Leaves the training state untouched."""
+        from . import regions as _rg
+        from .hydrology import analyse
+        from .step import LANE_OF
+        self.engine.sync()
+        ops = self.engine.ops[LANE_OF['dcgan_gen']]
+        x = labels_or_heightmap
+        if hasattr(x, "dtype") and np.asarray(x).ndim == 2 and np.asarray(x).dtype.kind in "iu" and np.asarray(x).dtype != np.uint8:
+            labels = x
+        elif of == 'lakes':
+            labels = _rg.lakes(analyse(ops, x, keep=('depth',)), **({"lake_min_depth": kw.pop("lake_min_depth")} if "lake_min_depth" in kw else {}))
+        elif of == 'basins':
+            labels = _rg.basins(analyse(ops, x, keep=('basin',)))
+        elif of == 'land':
+            if "sea_level" not in kw:
+                raise ValueError("of='land' needs sea_level")
+            labels = _rg.land(x, kw.pop("sea_level"))
+        elif of == 'bands':
+            labels = _rg.bands(x, kw.pop("levels", None))
+        else:
+            raise ValueError("of must be 'lakes', 'basins', 'land' or 'bands', got %r" % (of,))
+        return _rg.regions(ops, labels, areas, form=form, **kw)
+
+    def paint_regions(self, texture, regions, colour=None, opacity=0.6, outline=False):
+        """A texture (this model's generators' or the uint8 paths', of the regions' plane's size) with the polygons of a
+        regions.Regions filled -- outline=True: their cells along the rings only -- by the hydrology's paint kernel (DESIGN
+        §4zb); colour: default the water's.  Not in the reference.  Unpainted pixels keep their bits.  Leaves the training state
+        untouched."""
+        from .hydrology import Water
+        from .regions import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, regions, Water().colour if colour is None else colour, opacity,
+                     outline, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -1,4 +1,4 @@
-"""What the one-shot terrain tools -- erosion, skylight, mesh, hydrology, route, earthworks, viewshed, contour, peaks, rivers, and the world's calls
+"""What the one-shot terrain tools -- erosion, skylight, mesh, hydrology, route, earthworks, viewshed, contour, peaks, rivers, regions, and the world's calls
 of them -- share on the host: the heightmap intake, the size limit of the plane kernels, the ``keep`` check and call-scoped device scratch.
 Nothing here touches the library: a device is whatever has ``alloc``, ``free`` and ``sync``."""
 import numpy as np

@@ -38,6 +38,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--contours OUT.{svg,geojson,npz} [--interval X] [--base X] [--count N] [--index-every N]]
         [--peaks OUT.{geojson,csv,npz} [--min-prominence X] [--top N]]
         [--rivers OUT.{svg,geojson,npz} [--river-threshold N] [--min-order N]]
+        [--regions OUT.{svg,geojson,npz} --of {lakes,basins,land,bands} [--sea-level X] [--min-cells N] [--no-holes]]
 """
 import argparse
 import collections
@@ -809,6 +810,30 @@ class TerrainWorld:
         hydro = self.hydrology(y0, x0, h, w, keep=('filled', 'depth', 'direction', 'accumulation'))
         return rivers(self._ops, hydro, network, origin=(y0, x0))
 
+    def regions(self, y0, x0, h, w, of='lakes', areas=None, form=None, sea_level=None, levels=None, **kw):
+        """the areas of ``self.heightmap(y0, x0, h, w)`` as polygons with holes (regions.Regions), heights mapped as
+        a scene's; a plain or an eroded world.  of: 'lakes' or 'basins' (``self.hydrology`` of the rectangle first), 'land'
+        (above sea_level, a number in [0, 1]) or 'bands' (between the levels of a contour.Levels); areas: a regions.Areas; kw:
+        regions.regions' (keep, max_edges).  The Regions' ``origin`` is (y0, x0) and its ``points`` are in world coordinates.
+        Polygons belong to the rectangle, whose edge closes them: a lake, a basin or a band the edge cuts ends there, with the
+        edge as part of its ring, and its cells count the rectangle's alone; lakes and basins besides are the rectangle's
+        drainage's.  Two rectangles do NOT agree where they overlap.  Nothing is cached and no seam is handled."""
+        from . import regions as _rg
+        y0, x0 = int(y0), int(x0)
+        if of == 'lakes':
+            labels = _rg.lakes(self.hydrology(y0, x0, h, w, keep=('depth',)))
+        elif of == 'basins':
+            labels = _rg.basins(self.hydrology(y0, x0, h, w, keep=('basin',)))
+        elif of == 'land':
+            if sea_level is None:
+                raise ValueError("of='land' needs sea_level")
+            labels = _rg.land(self._unit_height(y0, x0, h, w), sea_level)
+        elif of == 'bands':
+            labels = _rg.bands(self._unit_height(y0, x0, h, w), levels)
+        else:
+            raise ValueError("of must be 'lakes', 'basins', 'land' or 'bands', got %r" % (of,))
+        return _rg.regions(self._ops, labels, areas, origin=(y0, x0), form=form, **kw)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -1021,6 +1046,14 @@ def parse_args(argv):
                         "the sheet gets their blue lines")
     from . import rivers as _rivers
     _rivers.add_network_arguments(p)
+    p.add_argument("--regions", default=None, metavar="OUT",
+                   help="also write the region's areas in world coordinates as polygons with holes: .svg, .geojson or .npz; --of "
+                        "says which areas (bands takes the levels of --interval and --base); with --contours OUT.svg or OUT.geojson "
+                        "the sheet gets them filled beneath its lines")
+    p.add_argument("--of", default=None, choices=("lakes", "basins", "land", "bands"), help="the areas --regions writes")
+    p.add_argument("--sea-level", type=float, default=None, metavar="X", help="--of land: the sea level, in [0, 1]")
+    from . import regions as _regions
+    _regions.add_area_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
     argv = list(argv)
     for i in range(len(argv) - 2, -1, -1):
@@ -1043,9 +1076,26 @@ def parse_args(argv):
         if len(a.sources) > MAX_OBSERVERS:
             p.error("--viewshed takes at most %d --from cells" % MAX_OBSERVERS)
     chosen = (a.interval, a.base, a.count, a.index_every)
+    if a.regions is None:
+        if a.of is not None or a.sea_level is not None or (a.min_cells, a.holes) != (_regions.Areas().min_cells, True):
+            p.error("--of / --sea-level / --min-cells / --no-holes need --regions")
+    else:
+        if not a.regions.lower().endswith((".svg", ".geojson", ".npz")):
+            p.error("--regions writes .svg, .geojson or .npz")
+        if a.of is None:
+            p.error("--regions needs --of")
+        if (a.of == "land") != (a.sea_level is not None):
+            p.error("--of land and --sea-level go together")
+        try:
+            a.areas = _regions.Areas(a.min_cells, a.holes)
+            if a.sea_level is not None and not 0 <= a.sea_level <= 1:
+                raise ValueError("--sea-level must lie in [0, 1], got %r" % (a.sea_level,))
+            a.band_levels = _contour.Levels(a.interval, a.base)
+        except ValueError as e:
+            p.error(str(e))
     if a.contours is None:
         d = _contour.Levels()
-        if chosen != (d.interval, d.base, d.count, d.index_every):
+        if chosen != (d.interval, d.base, d.count, d.index_every) and not (a.of == "bands" and chosen[2:] == (d.count, d.index_every)):
             p.error("--interval / --base / --count / --index-every need --contours")
     else:
         if not a.contours.lower().endswith((".svg", ".geojson", ".npz")):
@@ -1155,10 +1205,15 @@ def main(argv=None):
         if a.rivers:
             blue = world.rivers(y0, x0, h, w, a.network)
             blue.save(a.rivers)
+        areas = None
+        if a.regions:
+            areas = world.regions(y0, x0, h, w, a.of, a.areas, sea_level=a.sea_level, levels=a.band_levels)
+            areas.save(a.regions)
         if a.contours:
             spot = found if a.contours.lower().endswith(".svg") else None
-            world.contours(y0, x0, h, w, a.levels).save(a.contours, peaks=spot,
-                                                        rivers=None if a.contours.lower().endswith(".npz") else blue)
+            flat = a.contours.lower().endswith(".npz")
+            world.contours(y0, x0, h, w, a.levels).save(a.contours, peaks=spot, rivers=None if flat else blue,
+                                                        **({} if flat or areas is None else {"regions": areas}))
         if a.earthworks:
             ground = world.earthworks(y0, x0, h, w, a.sources if a.routes else None, a.targets).height
             if a.earthworks.endswith(".npy"):
