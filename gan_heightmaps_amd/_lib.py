@@ -232,6 +232,12 @@ SIGNATURES = {
     "ghm_regions_count": [_p, _p, _i32, _p, _i32, _i32, _i32, _i64, _p, C.POINTER(_i64)],
     "ghm_regions_trace": [_p, _i32, _i32, _i32, _p, _p, _i64, _i64, C.POINTER(_i64), C.POINTER(_i32)],
     "ghm_regions_extract": [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32],
+    "ghm_climate_transport": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32],
+    "ghm_climate_spread": [_p, _p, _i32, _i32, _i32, _i32, _p, _i32],
+    "ghm_climate_biome": [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p,
+                          _i32],
+    "ghm_climate_discharge": [_p, _p, _i32, _p, _i32, _i32, _i32, C.c_uint32, _p, _i32, _p, _i32, _p, C.POINTER(_i32)],
+    "ghm_climate_paint": [_p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _i32, _f, _i32, _p, _i32],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],
@@ -297,6 +303,7 @@ _SPECIAL = {"ghm_last_error": ([], C.c_char_p), "ghm_bn_workspace": ([_i32], C.c
             "ghm_rivers_list_bytes": ([_i64], C.c_int64),
             "ghm_regions_workspace": ([_i32, _i32], C.c_int64),
             "ghm_regions_trace_bytes": ([_i64], C.c_int64),
+            "ghm_climate_workspace": ([_i32, _i32], C.c_int64),
             "ghm_swd_workspace": ([], C.c_int64),
             "ghm_swd_sort_max_chunk": ([], C.c_int32)}
 # (ghm_conv_bn_fused_supported returns its answer as the int return value: typed with the plain signatures)

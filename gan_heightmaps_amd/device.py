@@ -1588,6 +1588,51 @@ class Ops:
              _vp(ring_offsets_ptr), _vp(ring_polygon_ptr), _vp(ring_hole_ptr), _vp(seed_ptr), _vp(label_ptr), _vp(cells_ptr),
              _vp(polygon_ptr), int(p_pitch))
 
+    # climate (csrc/climate.hip, gan_heightmaps_amd/climate.py)
+    @staticmethod
+    def climate_workspace(H, W):
+        """bytes of device workspace climate_discharge needs for a plane of H x W, or -1"""
+        return int(_lib.load().ghm_climate_workspace(int(H), int(W)))
+
+    def climate_transport(self, zq_ptr, z_pitch, H, W, wind, form, sea_q, hum_q, evap_q, base_q, up_q, rec_q, raw_ptr, r_pitch):
+        """the rain every wind line drops, cell by cell: the int32 plane of quantised heights -> the uint32 plane at raw_ptr.
+        wind: 0 .. 7 = N NE E SE S SW W NW, where it comes from; form: 0 line, 1 staged, the same bits; asynchronous"""
+        call("ghm_climate_transport", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), int(wind), int(form), int(sea_q), int(hum_q),
+             int(evap_q), int(base_q), int(up_q), int(rec_q), _vp(raw_ptr), int(r_pitch))
+
+    def climate_spread(self, raw_ptr, r_pitch, H, W, spread, rain_ptr, o_pitch):
+        """the floor of the mean of raw over the (2 spread + 1)^2 window, clamped at the edges -> the uint32 plane at rain_ptr;
+        asynchronous"""
+        call("ghm_climate_spread", self.h, _vp(raw_ptr), int(r_pitch), int(H), int(W), int(spread), _vp(rain_ptr), int(o_pitch))
+
+    def climate_biome(self, zq_ptr, z_pitch, rain_ptr, r_pitch, H, W, sea_q, t0_q, lapse_q, lat_q, origin_row, t_edges, r_edges, table,
+                      ocean, temperature_ptr, t_pitch, biome_ptr, b_pitch):
+        """temperature (int32, 1/256 degree) and the biome label (int32) of every cell; t_edges, r_edges: quantised edges, ascending;
+        table: (len(t_edges) + 1) x (len(r_edges) + 1) labels, row-major; they travel by value; asynchronous"""
+        te, re_, tb = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (t_edges, r_edges, table))
+        if tb.size != (te.size + 1) * (re_.size + 1):
+            raise ValueError("the table has %d labels for %d x %d edges" % (tb.size, te.size, re_.size))
+        call("ghm_climate_biome", self.h, _vp(zq_ptr), int(z_pitch), _vp(rain_ptr), int(r_pitch), int(H), int(W), int(sea_q), int(t0_q),
+             int(lapse_q), int(lat_q), int(origin_row), te.ctypes.data if te.size else None, int(te.size),
+             re_.ctypes.data if re_.size else None, int(re_.size), tb.ctypes.data, int(ocean), _vp(temperature_ptr), int(t_pitch),
+             _vp(biome_ptr), int(b_pitch))
+
+    def climate_discharge(self, dir_ptr, d_pitch, rain_ptr, r_pitch, H, W, ref_q, discharge_ptr, q_pitch, effective_ptr, e_pitch,
+                          workspace_ptr):
+        """the rain that drains through every cell (uint64) and min(that // ref_q, 2^32 - 1) (uint32) over the hydrology's
+        directions.  Returns the doubling rounds; waits for the stream"""
+        rounds = C.c_int32(0)
+        call("ghm_climate_discharge", self.h, _vp(dir_ptr), int(d_pitch), _vp(rain_ptr), int(r_pitch), int(H), int(W), int(ref_q),
+             _vp(discharge_ptr), int(q_pitch), _vp(effective_ptr), int(e_pitch), _vp(workspace_ptr), C.byref(rounds))
+        return int(rounds.value)
+
+    def climate_paint(self, biome_ptr, b_pitch, H, W, tex_ptr, tex_pitch, channels, palette, opacity, out_u8, out_ptr, out_pitch):
+        """the biomes on a texture of ``channels`` fp32 planes -> out_ptr, fp32 or uint8; palette: float32 [labels, 4] on the host,
+        (r, g, b, has) in the texture's range, a row with has <= 0 leaves its biome's pixels alone; asynchronous"""
+        pal = np.ascontiguousarray(palette, np.float32).reshape(-1, 4)
+        call("ghm_climate_paint", self.h, _vp(biome_ptr), int(b_pitch), int(H), int(W), _vp(tex_ptr), int(tex_pitch), int(channels),
+             pal.ctypes.data if pal.size else None, int(pal.shape[0]), float(opacity), int(bool(out_u8)), _vp(out_ptr), int(out_pitch))
+
     # hydraulic erosion (csrc/erosion.hip, gan_heightmaps_amd/erosion.py)
     @staticmethod
     def erosion_tile():

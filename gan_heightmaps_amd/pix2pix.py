@@ -482,6 +482,39 @@ class Pix2Pix:
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, regions, Water().colour if colour is None else colour, opacity,
                      outline, value_range=self.is_b_grayscale)
 
+    def heightmap_climate(self, heightmap, weather=None, biomes=None, hydrology=False, form=None, **kw):
+        """The climate of a heightmap -- rain carried along the wind with its rain shadow, temperature from altitude and world
+        row, a biome per cell and, with hydrology, the rain-weighted discharge -- computed on the GPU
+        (gan_heightmaps_amd/climate.py).  Not in the reference.  heightmap: (H, W) or (1, H, W), uint8 or floats in
+        [0, 1]; weather: a climate.Weather; biomes: a climate.Biomes; hydrology: True analyses the drainage first, or a
+        hydrology.Hydrology that kept 'direction'; form: 'line' or 'staged', the same bits; kw: climate.analyse's (origin,
+        keep).  Returns a climate.Climate.  Intended use:
+
+            hydro = model.heightmap_hydrology(heightmap)
+            c = model.heightmap_climate(heightmap, Weather(wind='SW'), hydrology=hydro)
+            found = model.heightmap_rivers(c.hydrology(hydro))                        # rivers that are thin on the dry side
+            zones = model.heightmap_regions(regions.biomes(c), of='labels')           # biome polygons
+            trees = model.scatter_heightmap(heightmap, species, blocked=~c.mask('taiga', 'temperate forest'))
+            painted = model.paint_biomes(texture, c, 0.5)
+
+        Leaves the training state untouched."""
+        from .climate import analyse
+        from .hydrology import Hydrology, analyse as drainage
+        from .step import LANE_OF
+        self.engine.sync()
+        ops = self.engine.ops[LANE_OF['dcgan_gen']]
+        hydro = hydrology if isinstance(hydrology, Hydrology) else (drainage(ops, heightmap, keep=('direction',)) if hydrology else None)
+        return analyse(ops, heightmap, weather, biomes, hydro=hydro, form=form, **kw)
+
+    def paint_biomes(self, texture, climate, opacity=0.6):
+        """A texture (this model's generators' or the uint8 paths', of the climate's plane's size) with every pixel blended
+        towards its biome's colour in the chart by the climate's palette kernel.  Not in the reference.  The
+        pixels of a biome without a colour keep their bits.  Leaves the training state untouched."""
+        from .climate import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, climate, opacity, value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -4,7 +4,7 @@ as areas: an outer ring and its holes, in order, with the number of cells -- a G
 filled lakes of an SVG sheet.  Integers throughout, and equal to a definition in plain Python (tests/regions_ref.py) bit for bit.
 
 The plane is a label plane: int32 (H, W), a negative label means "no region".  ``lakes``, ``basins``, ``territories``, ``covered``,
-``land`` and ``bands`` make one on the host from what the other tools return.
+``land``, ``bands`` and ``biomes`` make one on the host from what the other tools return.
 
 1. Two cells belong together when they are 4-neighbours with equal non-negative labels.  A polygon is such a component; polygons are
    numbered in the order of their least cell (row W + col), the seed.
@@ -30,7 +30,7 @@ from .util import is_int as _is_int, is_number as _number, read_image
 from .viewshed import _check_colour, _check_opacity, _check_origin, _colour
 
 __all__ = ["KEEP", "FORMS", "DEFAULT_FORM", "Areas", "Regions", "regions", "report", "paint", "lakes", "basins", "territories", "covered",
-           "land", "bands", "parse_args", "main"]
+           "land", "bands", "biomes", "parse_args", "main"]
 
 KEEP = ('polygon',)
 FORMS = ('sweep', 'union')
@@ -401,6 +401,16 @@ def bands(heightmap, levels=None):
     if levels.count is not None:
         below = np.minimum(below, levels.count)
     return below.astype(np.int32)
+
+
+def biomes(climate):
+    """the biome label of every land cell of a climate.Climate that kept 'biome', -1 in the sea: a polygon per patch of one biome,
+    with ``Regions.label`` the chart's label"""
+    from .climate import Climate
+    if not isinstance(climate, Climate) or climate.biome is None:
+        raise ValueError("climate must be a Climate that kept 'biome'")
+    b = np.asarray(climate.biome, np.int32)
+    return np.where(b == climate.biomes.ocean, -1, b).astype(np.int32)
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------

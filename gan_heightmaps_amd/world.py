@@ -39,6 +39,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--peaks OUT.{geojson,csv,npz} [--min-prominence X] [--top N]]
         [--rivers OUT.{svg,geojson,npz} [--river-threshold N] [--min-order N]]
         [--regions OUT.{svg,geojson,npz} --of {lakes,basins,land,bands} [--sea-level X] [--min-cells N] [--no-holes]]
+        [--climate OUT_PREFIX [--wind D] [--sea-level X]]
 """
 import argparse
 import collections
@@ -834,6 +835,21 @@ class TerrainWorld:
             raise ValueError("of must be 'lakes', 'basins', 'land' or 'bands', got %r" % (of,))
         return _rg.regions(self._ops, labels, areas, origin=(y0, x0), form=form, **kw)
 
+    def climate(self, y0, x0, h, w, weather=None, biomes=None, hydrology=False, **kw):
+        """the climate of ``self.heightmap(y0, x0, h, w)`` (climate.Climate), heights mapped as a scene's; a plain
+        or an eroded world.  weather: a climate.Weather; biomes: a climate.Biomes; hydrology=True analyses the rectangle first
+        (``self.hydrology``) and adds the rain-weighted discharge and the effective area; kw: climate.analyse's (form, keep).
+        The Climate's ``origin`` is (y0, x0), and world row y0 + r enters the temperature of its row r.
+        ``temperature`` reads the cell and its world row alone, so it is a property of the world: two rectangles agree on it bit
+        for bit where they overlap.  ``rain``, ``biome``, ``discharge`` and ``effective_area`` are NOT: they belong to the
+        rectangle, whose upwind edge is where the vapour enters with the weather's humidity, just as its edge is the outlet of
+        its drainage.  Nothing is cached and no seam is handled."""
+        from . import climate as _cl
+        y0, x0 = int(y0), int(x0)
+        hm = self._unit_height(y0, x0, h, w)                      # (the first request binds _ops)
+        hydro = self.hydrology(y0, x0, h, w, keep=('direction',)) if hydrology else None
+        return _cl.analyse(self._ops, hm, weather, biomes, origin=(y0, x0), hydro=hydro, **kw)
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -1051,7 +1067,11 @@ def parse_args(argv):
                         "says which areas (bands takes the levels of --interval and --base); with --contours OUT.svg or OUT.geojson "
                         "the sheet gets them filled beneath its lines")
     p.add_argument("--of", default=None, choices=("lakes", "basins", "land", "bands"), help="the areas --regions writes")
-    p.add_argument("--sea-level", type=float, default=None, metavar="X", help="--of land: the sea level, in [0, 1]")
+    p.add_argument("--sea-level", type=float, default=None, metavar="X", help="--of land and --climate: the sea level, in [0, 1]")
+    p.add_argument("--climate", default=None, metavar="OUT_PREFIX",
+                   help="also write the region's climate: OUT_PREFIX.rain.npy, .temperature.npy and .biome.npy (a name that ends in "
+                        ".npz: one archive); --wind and --sea-level choose the weather")
+    p.add_argument("--wind", default=None, metavar="D", help="--climate: the side the wind comes from, N NE E SE S SW W or NW")
     from . import regions as _regions
     _regions.add_area_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
@@ -1077,20 +1097,30 @@ def parse_args(argv):
             p.error("--viewshed takes at most %d --from cells" % MAX_OBSERVERS)
     chosen = (a.interval, a.base, a.count, a.index_every)
     if a.regions is None:
-        if a.of is not None or a.sea_level is not None or (a.min_cells, a.holes) != (_regions.Areas().min_cells, True):
+        if a.of is not None or (a.sea_level is not None and a.climate is None) or (a.min_cells, a.holes) != (_regions.Areas().min_cells, True):
             p.error("--of / --sea-level / --min-cells / --no-holes need --regions")
     else:
         if not a.regions.lower().endswith((".svg", ".geojson", ".npz")):
             p.error("--regions writes .svg, .geojson or .npz")
         if a.of is None:
             p.error("--regions needs --of")
-        if (a.of == "land") != (a.sea_level is not None):
+        if (a.of == "land") != (a.sea_level is not None) and not (a.of != "land" and a.climate is not None):
             p.error("--of land and --sea-level go together")
         try:
             a.areas = _regions.Areas(a.min_cells, a.holes)
             if a.sea_level is not None and not 0 <= a.sea_level <= 1:
                 raise ValueError("--sea-level must lie in [0, 1], got %r" % (a.sea_level,))
             a.band_levels = _contour.Levels(a.interval, a.base)
+        except ValueError as e:
+            p.error(str(e))
+    if a.climate is None:
+        if a.wind is not None:
+            p.error("--wind needs --climate")
+    else:
+        from . import climate as _climate
+        try:
+            d = _climate.Weather()
+            a.weather = _climate.Weather(wind=d.wind if a.wind is None else a.wind, sea_level=d.sea_level if a.sea_level is None else a.sea_level)
         except ValueError as e:
             p.error(str(e))
     if a.contours is None:
@@ -1205,6 +1235,8 @@ def main(argv=None):
         if a.rivers:
             blue = world.rivers(y0, x0, h, w, a.network)
             blue.save(a.rivers)
+        if a.climate:
+            world.climate(y0, x0, h, w, a.weather).save(a.climate)
         areas = None
         if a.regions:
             areas = world.regions(y0, x0, h, w, a.of, a.areas, sea_level=a.sea_level, levels=a.band_levels)
