@@ -238,6 +238,9 @@ SIGNATURES = {
                           _i32],
     "ghm_climate_discharge": [_p, _p, _i32, _p, _i32, _i32, _i32, C.c_uint32, _p, _i32, _p, _i32, _p, C.POINTER(_i32)],
     "ghm_climate_paint": [_p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _i32, _f, _i32, _p, _i32],
+    "ghm_sunlight_zmax": [_p, _p, _i64, _p],
+    "ghm_sunlight_sun": [_p, _p, _i32, _i32, _i32, C.POINTER(_i64), _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _p, _i32, _p, _i32],
+    "ghm_sunlight_steps": [_p, _p, _i32, _i32, _i32, C.POINTER(_i64), _i32, _i32, _i32, _p, _p, _p, _i32],
     "ghm_erosion_init": [_p, _p, _i32, _i32, _i32, _f, _p, _i32],
     "ghm_erosion_iterate": [_p, C.POINTER(ErosionParams), _p, _p, _p, _i32, _i32, _i32, _i32, _i32],
     "ghm_erosion_emit": [_p, _p, _i32, _i32, _i32, _f, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32],

@@ -14,7 +14,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["ctx.hip", "conv_igemm.hip", "conv_lp.hip", "conv_small.hip", "conv_thin.hip", "conv_thin_lp.hip", "conv_split.hip", "conv_pool_bwd.hip", "conv_bilinear.hip", "elementwise.hip", "elementwise_q.hip", "optim.hip", "ema.hip", "comm.hip", "texture.hip", "terrain.hip", "world.hip", "render.hip", "erosion.hip", "swd.hip", "skylight.hip", "mesh.hip", "hydrology.hip", "route.hip", "earthworks.hip", "scatter.hip", "viewshed.hip", "contour.hip", "peaks.hip", "rivers.hip", "regions.hip", "climate.hip"]
+SOURCES = ["ctx.hip", "conv_igemm.hip", "conv_lp.hip", "conv_small.hip", "conv_thin.hip", "conv_thin_lp.hip", "conv_split.hip", "conv_pool_bwd.hip", "conv_bilinear.hip", "elementwise.hip", "elementwise_q.hip", "optim.hip", "ema.hip", "comm.hip", "texture.hip", "terrain.hip", "world.hip", "render.hip", "erosion.hip", "swd.hip", "skylight.hip", "mesh.hip", "hydrology.hip", "route.hip", "earthworks.hip", "scatter.hip", "viewshed.hip", "contour.hip", "peaks.hip", "rivers.hip", "regions.hip", "climate.hip", "sunlight.hip"]
 HEADERS = ["common.h", "relax.h", os.path.join("..", "..", "include", "ghm.h")]
 OUT = os.path.join(os.path.dirname(HERE), "libghm.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1390,6 +1390,37 @@ class Ops:
         call("ghm_viewshed_steps", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(obs.shape[0]), int(target_q),
              int(bool(accel)), _vp(top_ptr), _vp(steps_ptr), int(s_pitch))
 
+    # sunlight (csrc/sunlight.hip, gan_heightmaps_amd/sunlight.py)
+    @staticmethod
+    def _sunlight_table(table):
+        t = np.ascontiguousarray(table, np.int64)
+        if t.ndim != 2 or t.shape[1] != 9:
+            raise ValueError("sunlight: the positions are an integer table [n, 9] of (rows, gmaj, gmin, m_q, rise_q, s_y, s_x, s_z, w_q), "
+                             "got %s" % (t.shape,))
+        return t, (t.ctypes.data_as(C.POINTER(C.c_int64)) if t.size else None)
+
+    def sunlight_zmax(self, top_ptr, top_elems, zmax_ptr):
+        """the largest of the block maxima at top_ptr -> the int32 word at zmax_ptr; asynchronous"""
+        call("ghm_sunlight_zmax", self.h, _vp(top_ptr), int(top_elems), _vp(zmax_ptr))
+
+    def sunlight_sun(self, zq_ptr, z_pitch, H, W, table, target_q, accel, top_ptr, zmax_ptr, lit_ptr, l_pitch, mask_ptr, m_pitch,
+                     hours_ptr, h_pitch, energy_ptr, e_pitch):
+        """the sun positions of ``table`` -- a host table [n, 9] of (rows, gmaj, gmin, m_q, rise_q, s_y, s_x, s_z, w_q) -- over the
+        int32 plane at zq_ptr -> four uint32 planes: the positions that light each cell at lit_ptr, bit i for position i at
+        mask_ptr (optional, n <= 32), their hours in 1/256 at hours_ptr and the energy on the cell's slope at energy_ptr; accel:
+        jump runs of steps the block maxima at top_ptr prove clear (the same bits); zmax_ptr: sunlight_zmax's word; asynchronous"""
+        t, ptr = self._sunlight_table(table)
+        call("ghm_sunlight_sun", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(t.shape[0]), int(target_q),
+             int(bool(accel)), _vp(top_ptr), _vp(zmax_ptr), _vp(lit_ptr), int(l_pitch), _vp(mask_ptr), int(m_pitch), _vp(hours_ptr),
+             int(h_pitch), _vp(energy_ptr), int(e_pitch))
+
+    def sunlight_steps(self, zq_ptr, z_pitch, H, W, table, target_q, accel, top_ptr, zmax_ptr, steps_ptr, s_pitch):
+        """sunlight_sun's launches with the steps tested per cell, over all positions -> the uint32 plane at steps_ptr (a
+        measuring aid); asynchronous"""
+        t, ptr = self._sunlight_table(table)
+        call("ghm_sunlight_steps", self.h, _vp(zq_ptr), int(z_pitch), int(H), int(W), ptr, int(t.shape[0]), int(target_q),
+             int(bool(accel)), _vp(top_ptr), _vp(zmax_ptr), _vp(steps_ptr), int(s_pitch))
+
     # contours (csrc/contour.hip, gan_heightmaps_amd/contour.py)
     @staticmethod
     def contour_cells_bytes(H, W):

@@ -515,6 +515,33 @@ class Pix2Pix:
         self.engine.sync()
         return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, climate, opacity, value_range=self.is_b_grayscale)
 
+    def heightmap_sunlight(self, heightmap, sun=None, form=None, **kw):
+        """Where the sun shines on a heightmap -- per cell the sun positions that light it, their hours and the energy on its
+        slope -- by exact shadow rays on the GPU (gan_heightmaps_amd/sunlight.py).  Not in the reference.
+        heightmap: (H, W) or (1, H, W), uint8 or floats in [0, 1]; sun: a sunlight.Sun (default sunlight.Day().sun(), an equinox
+        day at 45 degrees north); form: 'plain' or 'accel', the same bits; kw: sunlight.sunlight's (origin, keep).  Returns a
+        sunlight.Sunlight.  Intended use:
+
+            light = model.heightmap_sunlight(heightmap, Day(latitude=47, declination=-23.44).sun())
+            vines = model.scatter_heightmap(heightmap, species, blocked=~light.mask_hours(6))
+            painted = model.paint_sunlight(texture, light, max_hours=2)
+
+        Leaves the training state untouched."""
+        from .sunlight import sunlight
+        from .step import LANE_OF
+        self.engine.sync()
+        return sunlight(self.engine.ops[LANE_OF['dcgan_gen']], heightmap, sun, form, **kw)
+
+    def paint_sunlight(self, texture, sunlight, max_hours, colour=(0.05, 0.05, 0.2), opacity=0.5):
+        """A texture (this model's generators' or the uint8 paths', of the sunlight's size) with the cells a sunlight.Sunlight
+        finds lit fewer than ``max_hours`` hours blended towards ``colour`` by the hydrology's paint kernel.  Not
+        in the reference.  Unpainted pixels keep their bits.  Leaves the training state untouched."""
+        from .sunlight import paint
+        from .step import LANE_OF
+        self.engine.sync()
+        return paint(self.engine.ops[LANE_OF['dcgan_gen']], texture, sunlight, max_hours, colour, opacity,
+                     value_range=self.is_b_grayscale)
+
     def render_terrain(self, heightmap, texture, camera, height_scale=None, sky=None, **kw):
         """A camera view of a heightmap and its texture (arrays as this model's generators or the uint8 paths return them),
         ray cast on the GPU (gan_heightmaps_amd/render.py).  Not in the reference.  camera: a render.Camera in

@@ -1,4 +1,4 @@
-"""What the one-shot terrain tools -- erosion, skylight, mesh, hydrology, route, earthworks, viewshed, contour, peaks, rivers, regions, climate, and the world's calls
+"""What the one-shot terrain tools -- erosion, skylight, mesh, hydrology, route, earthworks, viewshed, contour, peaks, rivers, regions, climate, sunlight, and the world's calls
 of them -- share on the host: the heightmap intake, the size limit of the plane kernels, the ``keep`` check and call-scoped device scratch.
 Nothing here touches the library: a device is whatever has ``alloc``, ``free`` and ``sync``."""
 import numpy as np
@@ -38,6 +38,7 @@ def as_plane(heightmap, *, lead=True, unit_range=False, raw=False, what=None):
         viewshed    True   True        True   None
         contour     True   True        True   None            (it takes the viewshed's; peaks takes the same)
         climate     True   True        True   None            (the viewshed's too)
+        sunlight    True   True        True   None            (the viewshed's too)
     """
     a = heightmap if hasattr(heightmap, "dtype") and hasattr(heightmap, "shape") else np.asarray(heightmap)
     shape = tuple(a.shape)

@@ -40,6 +40,7 @@ downstream of ``_acquire`` -- crops, textures, scenes, flights -- reads the erod
         [--rivers OUT.{svg,geojson,npz} [--river-threshold N] [--min-order N]]
         [--regions OUT.{svg,geojson,npz} --of {lakes,basins,land,bands} [--sea-level X] [--min-cells N] [--no-holes]]
         [--climate OUT_PREFIX [--wind D] [--sea-level X]]
+        [--sunlight OUT.{npz,png} [--latitude X] [--declination X]]
 """
 import argparse
 import collections
@@ -850,6 +851,24 @@ class TerrainWorld:
         hydro = self.hydrology(y0, x0, h, w, keep=('direction',)) if hydrology else None
         return _cl.analyse(self._ops, hm, weather, biomes, origin=(y0, x0), hydro=hydro, **kw)
 
+    def sunlight(self, y0, x0, h, w, sun=None, max_margin=1024, form=None):
+        """where the sun shines on ``self.heightmap(y0, x0, h, w)`` (sunlight.Sunlight), heights mapped as a
+        scene's; a plain or an eroded world.  sun: a sunlight.Sun (default sunlight.Day().sun()); form: the form.  The
+        rectangle is analysed grown by min(sun.reach, max_margin) cells on every side and cropped; the Sunlight's ``origin`` is
+        (y0, x0).  No ray reads further than the sun's reach from its cell, so where the reach fits the margin
+        (``Sunlight.exact``) sunlight is a property of the world: two rectangles agree bit for bit where they overlap, on every
+        plane.  Where the margin caps it the planes belong to the rectangle, whose grown edge lets the low sun in.  Nothing is
+        cached."""
+        from . import sunlight as _sl
+        y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+        sun = _sl._check_sun(sun)
+        if not _sl._is_int(max_margin) or max_margin < 0:
+            raise ValueError("max_margin must be an integer >= 0, got %r" % (max_margin,))
+        m = min(sun.reach, int(max_margin))
+        hm = self._unit_height(y0 - m, x0 - m, h + 2 * m, w + 2 * m)
+        whole = _sl.sunlight(self._ops, hm, sun, form, origin=(y0 - m, x0 - m))
+        return whole.crop(m, m, h, w, exact=sun.reach <= int(max_margin))
+
     def flight_plan(self, cameras, max_dist, window_mb=1024, snap=None, sky=None):
         """the scene windows ``flight`` moves through: [((y0, x0, h, w), first_frame, last_frame)].  Pure arithmetic, no
         device.  Frame k's footprint is cameras[k].footprint(max_dist).  Starting at frame i, a window takes the longest run of
@@ -1072,6 +1091,11 @@ def parse_args(argv):
                    help="also write the region's climate: OUT_PREFIX.rain.npy, .temperature.npy and .biome.npy (a name that ends in "
                         ".npz: one archive); --wind and --sea-level choose the weather")
     p.add_argument("--wind", default=None, metavar="D", help="--climate: the side the wind comes from, N NE E SE S SW W or NW")
+    p.add_argument("--sunlight", default=None, metavar="OUT",
+                   help="also write where the sun shines on the region over one day (sunlight's .npz, or a .png of the hours); "
+                        "--latitude and --declination choose the day")
+    p.add_argument("--latitude", type=float, default=None, metavar="X", help="--sunlight: degrees north (default 45)")
+    p.add_argument("--declination", type=float, default=None, metavar="X", help="--sunlight: the sun's declination in degrees (default 0)")
     from . import regions as _regions
     _regions.add_area_arguments(p)
     # a region or a cell that starts with a negative number would read as an option: hand it over in the --region=... form
@@ -1121,6 +1145,19 @@ def parse_args(argv):
         try:
             d = _climate.Weather()
             a.weather = _climate.Weather(wind=d.wind if a.wind is None else a.wind, sea_level=d.sea_level if a.sea_level is None else a.sea_level)
+        except ValueError as e:
+            p.error(str(e))
+    if a.sunlight is None:
+        if a.latitude is not None or a.declination is not None:
+            p.error("--latitude / --declination need --sunlight")
+    else:
+        from . import sunlight as _sunlight
+        if not (a.sunlight.endswith(".npz") or a.sunlight.lower().endswith(".png")):
+            p.error("--sunlight writes .npz or .png")
+        try:
+            d = _sunlight.Day()
+            a.sun = _sunlight.Day(d.latitude if a.latitude is None else a.latitude,
+                                  d.declination if a.declination is None else a.declination).sun()
         except ValueError as e:
             p.error(str(e))
     if a.contours is None:
@@ -1237,6 +1274,8 @@ def main(argv=None):
             blue.save(a.rivers)
         if a.climate:
             world.climate(y0, x0, h, w, a.weather).save(a.climate)
+        if a.sunlight:
+            world.sunlight(y0, x0, h, w, a.sun).save(a.sunlight)
         areas = None
         if a.regions:
             areas = world.regions(y0, x0, h, w, a.of, a.areas, sea_level=a.sea_level, levels=a.band_levels)
